@@ -13,7 +13,14 @@ step = the whole reference eval (visreps/evals.py:222-400):
     RandomState(42) index sets drawn inside the step.
 Inputs (images, responses) are resident in HBM before timing starts.
 
-  python bench.py [--gpus N --steps K --warmup W]   (N > 1 under torch.distributed.run)
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+                                                     (N > 1 under torch.distributed.run)
+
+A plain run sets up, warms up, times the K steps, writes the last step's results if
+--dump-outputs is given (dump_outputs) and prints the line; its roofline figures come from
+HIP events inside the timed steps. --full adds the runs the headline does not need, after
+the timed steps: the exact-form step, the structured-RDM EST probe, the Kendall and
+configs[2]/[3]/[4] legs and `cpu_baseline` (null in a plain run's line).
 
 Rank 0 prints one JSON line. `roofline` is the bootstrap engine (the dominant cost): the
 engine's own algorithmic HBM bytes per call (pipeline.engine_call_bytes) / its HIP-event
@@ -32,7 +39,10 @@ import json
 import math
 import os
 import sys
+import tempfile
 import time
+
+T_START = time.perf_counter()
 
 # MIOpen find (NORMAL) + cudnn.benchmark pick the convolution kernels by timing them during
 # warm-up: CustomCNN extraction of 10k images 349 -> 239 ms against FAST's heuristic choice
@@ -540,6 +550,38 @@ def configs2_leg(dev) -> dict:
     return out
 
 
+def dump_outputs(out_dir: str, res: dict, neural: dict, sel: dict, points, regions, n: int) -> None:
+    """--dump-outputs: what the last timed step returned, as .npy files under out_dir (units
+    in point-major order, regions and points in the bench's own order):
+      unit_scores.npy       (units, 1 + n_boot) float64: point Spearman, then the bootstrap scores
+      unit_ci.npy           (units, 2) float64: the 2.5 / 97.5 percentiles (absent with --boot 0)
+      phase1_scores.npy     (regions, points) float64: phase 1's selection Spearmans
+      phase1_best.npy       (regions,) float64: index of the best point per region
+      neural_rdm_rows.npy   (regions held by this rank, 64, N) float32: 64 rows of every neural
+                            RDM of the step (RandomState(0).choice(N, 64), sorted), 10 MB at
+                            N = 10k; the whole RDMs are 400 MB each
+    The inputs are seeded, so two builds run with the same arguments can be compared file by
+    file (the fc GEMMs of the extraction are not bit-reproducible run to run: 4e-7)."""
+    os.makedirs(out_dir, exist_ok=True)
+    units = [(p, r) for p in points for r in regions]
+    scores = np.asarray([[res[u]["score"]] + list(res[u].get("bootstrap_scores", [])) for u in units],
+                        dtype=np.float64)
+    np.save(os.path.join(out_dir, "unit_scores.npy"), scores)
+    if scores.shape[1] > 1:
+        np.save(os.path.join(out_dir, "unit_ci.npy"),
+                np.asarray([[res[u]["ci_low"], res[u]["ci_high"]] for u in units], dtype=np.float64))
+    np.save(os.path.join(out_dir, "phase1_scores.npy"),
+            np.asarray([[e["score"] for e in sel[r][1]] for r in regions], dtype=np.float64))
+    np.save(os.path.join(out_dir, "phase1_best.npy"),
+            np.asarray([list(points).index(sel[r][0]) for r in regions], dtype=np.float64))
+    held = [r for r in regions if r in neural and tuple(neural[r].shape) == (n, n)]
+    if held:
+        rows = np.sort(np.random.RandomState(0).choice(n, min(64, n), replace=False))
+        rows_t = torch.as_tensor(rows, dtype=torch.long, device=neural[held[0]].device)
+        np.save(os.path.join(out_dir, "neural_rdm_rows.npy"),
+                np.stack([neural[r][rows_t].float().cpu().numpy() for r in held]))
+
+
 def _time(fn):
     t = time.perf_counter()
     out = fn()
@@ -608,7 +650,7 @@ def cpu_baseline(n: int, n_boot: int, dims: dict, voxels: dict, model, images) -
     return {"value": round(total, 1), "unit": "s", "cores": threads, "kind": "port", "sample": sample}
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
@@ -616,13 +658,41 @@ def main():
     ap.add_argument("--n", "--stimuli", dest="n", type=int, default=10000)
     ap.add_argument("--boot", type=int, default=1000)
     ap.add_argument("--batch", type=int, default=128)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-est-probe", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the Kendall and configs[2]/[3]/[4] legs")
-    ap.add_argument("--no-exact-step", action="store_true", help="skip the exact-form step after the timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline does not need: the exact-form step, "
+                         "the structured-RDM EST probe, the Kendall and configs[2]/[3]/[4] legs and the CPU "
+                         "baseline (each can be dropped again with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/<name>.npy (bench.dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-est-probe", action="store_true", help="with --full: skip the structured-RDM EST probe")
+    ap.add_argument("--no-extra-legs", action="store_true",
+                    help="with --full: skip the Kendall and configs[2]/[3]/[4] legs")
+    ap.add_argument("--no-exact-step", action="store_true",
+                    help="with --full: skip the exact-form step after the timed steps")
     ap.add_argument("--legs", default="kendall,configs3,configs4,configs2",
-                    help="comma list of extra legs (outside the timed steps) to run at N = 1")
-    args = ap.parse_args()
+                    help="with --full: comma list of extra legs (outside the timed steps) to run at N = 1")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu_baseline = args.no_est_probe = args.no_extra_legs = args.no_exact_step = True
+    return args
+
+
+# MIOpen's find runs every applicable solver at the first call of a shape and compiles each
+# one's kernels: 24 s for the bench's 10 (convolution, batch) shapes. These three never come
+# within 2x of the winner on any of them (profiles/bench_miopen_find.log): GEMM (im2col +
+# rocBLAS) is 7-10x behind, the naive direct kernel 20x, Winograd F(3x2) 2x behind F(2x3).
+# Without them the first calls take 9 s and every shape keeps its winner.
+MIOPEN_FIND_SKIP = ("MIOPEN_DEBUG_CONV_GEMM", "MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_FWD",
+                    "MIOPEN_DEBUG_AMD_WINOGRAD_RXS_F3X2")
+
+
+def main():
+    args = parse_args()
+    for k in MIOPEN_FIND_SKIP:  # (here, not at import: MIOpen reads them at the first convolution)
+        os.environ.setdefault(k, "0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -648,27 +718,44 @@ def main():
     rows = shard_rows(N, rank, world)
 
     torch.manual_seed(0)  # identical random-init weights on every rank
-    model = CustomCNN(num_classes=1000).to(dev).eval()
+    model = CustomCNN(num_classes=1000).eval()
     extractor = FeatureExtractor(model, LAYERS, extract_pre_and_post=True)
     points = list(extractor.return_nodes)
-    images = make_images(rows, device=dev)
-    responses = make_responses(images, rows, NSD_ROIS_4)
-    torch.cuda.synchronize()
+    # the points' widths from a host forward of one blank image, before the model moves to the
+    # device: a probe batch on the device would have MIOpen tune every convolution for a
+    # batch shape that no step runs
+    dims = {}
+    with torch.no_grad():
+        for p, f in extractor(torch.zeros(1, 3, 224, 224)).items():
+            dims[p] = f[0].numel()
+    extractor.features.clear()
+    model.to(dev)
 
     # SRP matrices of the phase-1 projection (sklearn construction, seeded so every rank
     # holds the same ones; the reference fits them once and caches them, so they are built
-    # before timing): one per distinct point width
-    dims = {}
-    with torch.no_grad():
-        for p, f in extractor(images[:2]).items():
-            dims[p] = f[0].numel()
+    # before timing): one per distinct point width. An uncached fit takes seconds per matrix
+    # on the host, so the fits run on a host thread under the input generation and the first
+    # warm-up's extraction; srp_projectors() waits for them and uploads the matrices.
+    from concurrent.futures import ThreadPoolExecutor
+
     from visreps_amd.analysis.sparse_random_projection import SparseProjector, get_srp_transformer
 
-    cache = os.path.join("/tmp", f"visreps_srp_cache_{os.getuid()}")
-    proj_by_d = {d: SparseProjector(get_srp_transformer(D=d, k=min(4096, d), density=None, seed=0,
-                                                        cache_dir=cache), dev)
-                 for d in sorted(set(dims.values()))}
-    projectors = {p: proj_by_d[d] for p, d in dims.items()}
+    cache = os.path.join(tempfile.gettempdir(), f"visreps_srp_cache_{os.getuid()}")
+    srp_pool = ThreadPoolExecutor(1)
+    srp_fits = {d: srp_pool.submit(get_srp_transformer, D=d, k=min(4096, d), density=None, seed=0, cache_dir=cache)
+                for d in sorted(set(dims.values()))}
+    projectors = {}
+
+    def srp_projectors():
+        if not projectors:
+            proj_by_d = {d: SparseProjector(f.result(), dev) for d, f in srp_fits.items()}
+            projectors.update({p: proj_by_d[d] for p, d in dims.items()})
+        return projectors
+
+    images = make_images(rows, device=dev)
+    responses = make_responses(images, rows, NSD_ROIS_4)
+    torch.cuda.synchronize()
+    t_inputs = time.perf_counter() - T_START
 
     # who computes and who reads every RDM of the step (the same on every rank): owners get
     # the full rows of their RDMs, consumers the packed tiles (pipeline.make_schedule)
@@ -682,8 +769,6 @@ def main():
     prefetch = os.environ.get("VISREPS_PLAN_PREFETCH", "0") == "1"
     plan_stream = torch.cuda.Stream(device=dev) if prefetch else None
     _, _, keep = phase1_rows(N, 1000, 42, rank, world)
-
-    from concurrent.futures import ThreadPoolExecutor
 
     draw_pool = ThreadPoolExecutor(1)
 
@@ -704,7 +789,7 @@ def main():
         # and stream under phase 1
         ex = ShardedRDMs(sched, rows, pg, times, exchange_pg=feat_pg)
         ex.start()
-        sel = phase1_select(feats, projectors, responses, points, N, n_select=1000, seed=42,
+        sel = phase1_select(feats, srp_projectors(), responses, points, N, n_select=1000, seed=42,
                             pg=pg, times=times, selected_rows=sel_rows)
         ev[2].record()
         # this rank's RDMs: its pieces' Grams + the exchange of the rest; the rank plans of the
@@ -721,12 +806,19 @@ def main():
         times.phases(["extract", "phase1", "rdms", "units"], ev)
         return res, neural, sel
 
+    log(f"[rank {rank}] setup: {time.perf_counter() - T_START:.2f}s since start "
+        f"(imports, model and inputs {t_inputs:.2f}s; SRP fits still running: "
+        f"{sum(not f.done() for f in srp_fits.values())})")
     for w in range(args.warmup):
         t = time.perf_counter()
-        step(StepTimes())
+        wt = StepTimes()
+        step(wt)
         torch.cuda.synchronize()
-        log(f"[rank {rank}] warmup {w}: {time.perf_counter() - t:.2f}s")
+        wt.resolve()
+        log(f"[rank {rank}] warmup {w}: {time.perf_counter() - t:.2f}s "
+            f"{ {k: round(v) for k, v in wt.phase_ms.items()} } ms")
 
+    srp_projectors()  # (--warmup 0: the fits end before the timing starts)
     L = lib()
     if pg is not None:
         dist.barrier()
@@ -758,6 +850,8 @@ def main():
         elapsed = float(mx[0])
     per_step = elapsed / args.steps
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, neural, sel, points, regions, N)
     first_unit = res[(points[0], "V1")]
     # the headline for RDMs whose subsets break the EST window (structured fMRI RDMs go exact
     # up front): one more whole step with every engine pass in the exact chunk-base form

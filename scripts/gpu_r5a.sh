@@ -5,7 +5,7 @@ set -o pipefail
 out=gpurun_out/${1:-r5a}
 mkdir -p $out
 export TMPDIR=/tmp
-timeout -k 10 500 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-est-probe > $out/bench.json 2> $out/bench.err \
+timeout -k 10 500 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-est-probe > $out/bench.json 2> $out/bench.err \
     || { echo "bench failed"; tail -20 $out/bench.err; exit 1; }
 python3 - $out/bench.json <<'PY'
 import json, sys
