@@ -417,7 +417,13 @@ def bootstrap_full(
     sub-RDMs A[idx][:, idx], B[idx][:, idx], read in place (vr_spearman_full_subset_f32 /
     vr_kendall_full_subset_f32: radix sorts, exact integer statistics, so every score equals
     the rank-plan engines' where both run). float64 scores on the device, the full set first
-    when full_first. Works at any n with n(n-1)/2 < 2^32."""
+    when full_first. Works at any n with n(n-1)/2 < 2^32.
+
+    Each draw is read in ascending stimulus order (its indices are sorted first), which gives
+    the draw's own statistic only for symmetric RDMs: a pair (i, j) drawn as (j, i) is read at
+    [i, j]. A NaN makes the scores of the draws that contain it NaN and no others (the
+    reference's per-draw behaviour). idx outside [0, n) raises ValueError: the kernels read
+    rdm[idx[a], idx[b]] unchecked."""
     method = method.lower()
     if method not in _ENGINES:
         raise ValueError(f"bootstrap engine for compare_method={method!r}: spearman or kendall")
@@ -434,6 +440,9 @@ def bootstrap_full(
     # any order): read each sub-RDM in ascending stimulus order, whose rows and columns are
     # then nearly contiguous in memory (coalesced) instead of gathered at random
     if idx_t.numel():
+        lo, hi = int(idx_t.min()), int(idx_t.max())
+        if lo < 0 or hi >= n:
+            raise ValueError(f"idx must lie in [0, {n}): found {lo if lo < 0 else hi}")
         idx_t = torch.sort(idx_t, dim=1).values
     total = n_sets + (1 if full_first else 0)
     scores = torch.empty(total, dtype=torch.float64, device=dev)

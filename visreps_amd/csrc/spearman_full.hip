@@ -388,7 +388,7 @@ __global__ __launch_bounds__(256) void k_tab_range(const float* __restrict__ A, 
     for (int q = 1; q < 4; ++q) v = (c & 1) ? max(v, red[q][c]) : min(v, red[q][c]);
     mmpart[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + c] = v;
   }
-  if (threadIdx.x == 0 && bad) {
+  if ((threadIdx.x & 63) == 0 && bad) {  // bad is reduced per wave: every wave leader publishes
     if (bad & 1u) atomicOr(&nan[0], 1u);
     if (bad & 2u) atomicOr(&nan[1], 1u);
   }
