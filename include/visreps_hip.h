@@ -319,6 +319,32 @@ int vr_bootstrap_kendall_plans(const void* planA, const void* planB, int64_t n,
                                const int32_t* idx, int64_t k, int64_t n_sets, int full_first,
                                double* scores, void* ws, size_t ws_bytes, void* stream);
 
+/* Pearson of the sub-RDMs A[idx][:, idx], B[idx][:, idx] (k rows idx [dev] int32 into the
+ * n x n RDMs, read in place at the upper-triangle entry of each pair): one bootstrap draw of
+ * rsa.py:233-261 with compare_method="pearson", the two fp64 passes of vr_pearson_triu_f32.
+ * out [dev] one double (NaN for k <= 2, non-finite input, a constant sub-triangle).
+ * idx must lie in [0, n): the kernels read unchecked. */
+size_t vr_pearson_triu_subset_workspace(int64_t k);
+int vr_pearson_triu_subset_f32(const float* A, const float* B, int64_t n, int64_t ld,
+                               const int32_t* idx, int64_t k, double* out,
+                               void* ws, size_t ws_bytes, void* stream);
+
+/* Bootstrapped Pearson RSA on the RDMs themselves: the bootstrap loop of evals.py:355-373 /
+ * rsa.py:233-261 with compare_method="pearson" as one masked fp64-MFMA GEMM over all
+ * subsets (csrc/pearson_boot.hip). idx, k, n_sets, full_first and the scores layout as
+ * vr_bootstrap_spearman_plans (idx may be null when n_sets == 0); A, B [dev] (n, n) row-major
+ * fp32 with leading dimension ld. Preconditions as for the rank-plan engines: the rows of
+ * idx hold distinct indices in [0, n), and the RDMs are symmetric (the upper triangle is
+ * read whatever the order of idx). No n <= 65,535 limit. A subset scores NaN for k <= 2, when
+ * it contains a non-finite pair (and only then) or when a sub-triangle is constant; scores
+ * are bit-identical run to run. Synchronises the stream once (the flags of the subsets that
+ * the two-pass kernels recompute). Workspace: vr_bootstrap_pearson_workspace(n, n_sets)
+ * covers up to n_sets subsets plus the full set. */
+size_t vr_bootstrap_pearson_workspace(int64_t n, int64_t n_sets);
+int vr_bootstrap_pearson_f32(const float* A, const float* B, int64_t n, int64_t ld,
+                             const int32_t* idx, int64_t k, int64_t n_sets, int full_first,
+                             double* scores, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------
  * Phase-1 sparse random projection (extraction side).
  * Replaces torch.sparse.mm(P, flat.t()).t() (visreps/models/utils.py:334-336) with P the

@@ -93,6 +93,16 @@ _PROTOTYPES = {
         ctypes.c_int,
         [_vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_sz, _vp],
     ),
+    "vr_pearson_triu_subset_workspace": (_c_sz, [_c_i64]),
+    "vr_pearson_triu_subset_f32": (
+        ctypes.c_int,
+        [_vp, _vp, _c_i64, _c_i64, _vp, _c_i64, _vp, _vp, _c_sz, _vp],
+    ),
+    "vr_bootstrap_pearson_workspace": (_c_sz, [_c_i64, _c_i64]),
+    "vr_bootstrap_pearson_f32": (
+        ctypes.c_int,
+        [_vp, _vp, _c_i64, _c_i64, _vp, _c_i64, _c_i64, ctypes.c_int, _vp, _vp, _c_sz, _vp],
+    ),
     "vr_bootstrap_workspace": (_c_sz, [_c_i64]),
     "vr_bootstrap_spearman_plans": (
         ctypes.c_int,

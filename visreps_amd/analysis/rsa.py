@@ -9,6 +9,8 @@ arithmetic runs in the HIP kernels of libvisreps_hip.so:
                                           Pearson: fp64 two-pass triangle reduction
   compute_rsa             rsa.py:132-281  layer selection + point + bootstrap on device
   bootstrap_rsa           evals.py:355-373 the inline NSD/TVSD bootstrap, batched
+  bootstrap_pearson       rsa.py:233-261  the same loop with compare_method="pearson": all
+                                          draws as one masked GEMM on the fp64 MFMA
 
 Tensors on a HIP device stay there; CPU tensors are copied to the current device and
 results come back on the CPU (the reference's own return device). There is no CPU
@@ -43,6 +45,7 @@ __all__ = [
     "bootstrap_spearman_multi",
     "bootstrap_spearman_grid",
     "bootstrap_kendall",
+    "bootstrap_pearson",
     "bootstrap_full",
     "spearman_full",
     "percentile",
@@ -471,6 +474,56 @@ def bootstrap_full(
     return scores
 
 
+def bootstrap_pearson(
+    rdm_a: torch.Tensor,
+    rdm_b: torch.Tensor,
+    idx: Optional[np.ndarray | torch.Tensor],
+    *,
+    full_first: bool = True,
+) -> torch.Tensor:
+    """Pearson of triu(A[s][:, s]) vs triu(B[s][:, s]) for every subset s (row of idx),
+    preceded by the full set when full_first: the bootstrap of evals.py:355-373 /
+    rsa.py:233-261 with compare_method="pearson" (vr_bootstrap_pearson_f32: all subsets as one
+    masked GEMM on the fp64 MFMA, no per-draw gather). float64 scores on the device.
+
+    Takes the RDMs themselves, at any n (Pearson needs no rank plan). As for the plan engines
+    the rows of idx hold distinct indices and the RDMs are symmetric: each pair is read at its
+    upper-triangle entry. A subset scores NaN when it contains a non-finite pair (no other
+    subset does), when one of its sub-triangles is constant, or for k <= 2. idx outside [0, n)
+    raises ValueError."""
+    dev = _device_for(rdm_a, rdm_b)
+    a, b = _as_device_f32(rdm_a, dev), _as_device_f32(rdm_b, dev)
+    if a.shape != b.shape or a.ndim != 2 or a.size(0) != a.size(1):
+        raise ValueError("RDMs must share the same square 2-D shape")
+    if a.stride(0) != b.stride(0):
+        a, b = a.contiguous(), b.contiguous()
+    n = int(a.size(0))
+    idx_t = _idx_tensor(idx, dev)
+    n_sets, k = (int(idx_t.size(0)), int(idx_t.size(1))) if idx_t.numel() else (0, 0)
+    if k > n:
+        raise ValueError(f"idx rows hold distinct stimuli: k = {k} > n = {n}")
+    if idx_t.numel():
+        lo, hi = int(idx_t.min()), int(idx_t.max())
+        if lo < 0 or hi >= n:
+            raise ValueError(f"idx must lie in [0, {n}): found {lo if lo < 0 else hi}")
+    total = n_sets + (1 if full_first else 0)
+    scores = torch.empty(total, dtype=torch.float64, device=dev)
+    if total == 0:
+        return scores
+    L = lib()
+    ws = workspace.get(dev, L.vr_bootstrap_pearson_workspace(n, n_sets), "pearson_boot")
+    with torch.cuda.device(dev):
+        check(
+            L.vr_bootstrap_pearson_f32(
+                _ptr(a), _ptr(b), n, a.stride(0) if n else 0,
+                _ptr(idx_t) if idx_t.numel() else None, k, n_sets, int(full_first),
+                _ptr(scores), _ptr(ws), ws.numel(), stream_of(dev),
+            ),
+            "vr_bootstrap_pearson_f32",
+        )
+    return scores
+
+
 def percentile(scores: np.ndarray, q: float) -> float:
     """numpy.percentile(scores, q), linear method (evals.py:371-372)."""
     a = np.ascontiguousarray(scores, dtype=np.float64)
@@ -645,14 +698,22 @@ def bootstrap_rsa(
     """Point estimate plus the reference's inline bootstrap: a fresh RandomState(seed),
     n_bootstrap draws of choice(n, int(0.9 n), replace=False), Spearman (or Kendall tau-a)
     of the two sub-RDMs per draw, 2.5/97.5 linear percentiles. Returns
-    (point, scores[n_bootstrap], ci_low, ci_high)."""
+    (point, scores[n_bootstrap], ci_low, ci_high).
+
+    method="pearson" runs bootstrap_pearson on the RDM tensors; a RankPlan argument raises
+    ValueError there, since a plan does not keep its RDM."""
+    pearson = method.lower() == "pearson"
     engine = _ENGINES.get(method.lower())
-    if engine is None:
-        raise ValueError(f"bootstrap engine for compare_method={method!r}: spearman or kendall")
+    if engine is None and not pearson:
+        raise ValueError(f"bootstrap engine for compare_method={method!r}: spearman, kendall or pearson")
+    if pearson and (isinstance(model_rdm, RankPlan) or isinstance(neural_rdm, RankPlan)):
+        raise ValueError("method='pearson' needs the RDM tensors: a RankPlan does not keep its RDM")
     n = model_rdm.n if isinstance(model_rdm, RankPlan) else int(model_rdm.shape[0])
     if idx is None:
         idx = bootstrap_indices(seed, n, int(n * 0.9), int(n_bootstrap)) if n_bootstrap else None
-    if n > PLAN_MAX_N and not isinstance(model_rdm, RankPlan):  # beyond the rank plans
+    if pearson:
+        scores = bootstrap_pearson(model_rdm, neural_rdm, idx, full_first=True).cpu().numpy()
+    elif n > PLAN_MAX_N and not isinstance(model_rdm, RankPlan):  # beyond the rank plans
         scores = bootstrap_full(model_rdm, neural_rdm, idx, method=method, full_first=True).cpu().numpy()
     else:
         pa = model_rdm if isinstance(model_rdm, RankPlan) else RankPlan(model_rdm)
@@ -745,13 +806,16 @@ def compute_rsa(
 
     ci_low, ci_high = None, None
     bootstrap_scores_list = None
-    if engine is not None and n_test > 1:
+    batched = engine is not None or (method == "pearson" and bootstrap)
+    if batched and n_test > 1:
         boot_idx = None
         if bootstrap and n_bootstrap > 0:
             k = int(n_test * 0.9)
             boot_idx = np.stack([rng.choice(n_test, size=k, replace=False)
                                  for _ in range(n_bootstrap)]).astype(np.int32)
-        if n_test > PLAN_MAX_N:  # beyond the rank plans: one plan-free call per draw
+        if engine is None:  # pearson: all draws in one call on the RDMs, at any n
+            scores = bootstrap_pearson(test_model_rdm, test_neural_rdm, boot_idx, full_first=True).cpu().numpy()
+        elif n_test > PLAN_MAX_N:  # beyond the rank plans: one plan-free call per draw
             scores = bootstrap_full(test_model_rdm, test_neural_rdm, boot_idx, method=method).cpu().numpy()
         else:
             plan_m, plan_n = RankPlan(test_model_rdm), RankPlan(test_neural_rdm)

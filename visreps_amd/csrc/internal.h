@@ -36,6 +36,12 @@ int radix_pass_k(const uint32_t* ki, uint32_t* ko, int64_t n, int shift, uint32_
 int radix_sort_kv(uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, uint32_t* vals_alt,
                   int64_t n, uint32_t* ws, hipStream_t st);
 
+// ---- two-pass fp64 Pearson of two RDM triangles (pearson.hip) ----------------------
+// idx == nullptr: the full n_or_k x n_or_k triangle; else the sub-RDM of the n_or_k stimuli
+// idx[0..n_or_k), read in place. part: 5 n_or_k doubles, mu: 2 doubles, out: 1 double.
+int pearson_two_pass(const float* A, const float* B, int64_t n_or_k, int64_t ld, const int32_t* idx,
+                     double* out, double* part, double* mu, hipStream_t st);
+
 // ---- block-level helpers -----------------------------------------------------------
 // Exclusive scan across a block of BS threads (BS multiple of 64, <= 1024).
 // lds must hold BS/64 + 1 uint32. Returns this thread's exclusive prefix; total = sum.

@@ -2,20 +2,35 @@
 // compute_rdm_correlation(.., correlation="Pearson") -> scipy.stats.pearsonr
 // (visreps/analysis/rsa.py:43-47,121-122). Two passes (means, then centred sums) with
 // fixed-order reductions, so the result is deterministic.
+//
+// The same two passes over a sub-RDM A[idx][:, idx] read in place (k_pearson_rows<true>,
+// vr_pearson_triu_subset_f32): one bootstrap draw of rsa.py:233-261 with
+// compare_method="pearson". The bootstrap engine over many draws is pearson_boot.hip; it
+// falls back on these two passes for the draws its one-pass sums cannot decide.
 #include "internal.h"
 
 namespace vr {
 
+// SUB: row a and column b are positions in idx (k of them, n = k); the pair is read at the
+// upper-triangle entry [min(idx[a], idx[b]), max(..)] whatever the order of idx.
+template <bool SUB>
 __global__ __launch_bounds__(256) void k_pearson_rows(const float* __restrict__ A,
                                                       const float* __restrict__ B, int64_t n,
-                                                      int64_t ld, const double* __restrict__ mu,
+                                                      int64_t ld, const int32_t* __restrict__ idx,
+                                                      const double* __restrict__ mu,
                                                       double* __restrict__ part) {
   __shared__ double red[5][4];
   const int64_t a = blockIdx.x;
   double s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0;
   const double ma = mu ? mu[0] : 0.0, mb = mu ? mu[1] : 0.0;
+  const int64_t ia = SUB ? (int64_t)idx[a] : a;
   for (int64_t b = a + 1 + threadIdx.x; b < n; b += 256) {
-    const double x = (double)A[a * ld + b], y = (double)B[a * ld + b];
+    int64_t at = a * ld + b;
+    if constexpr (SUB) {
+      const int64_t ib = idx[b];
+      at = ia < ib ? ia * ld + ib : ib * ld + ia;
+    }
+    const double x = (double)A[at], y = (double)B[at];
     if (!mu) {
       s0 += x;
       s1 += y;
@@ -76,6 +91,24 @@ __global__ __launch_bounds__(256) void k_pearson_reduce(const double* __restrict
   }
 }
 
+// The two passes on stream st: idx == nullptr the full n x n triangle, else the k x k
+// sub-RDM (n_or_k = k). part: 5 n_or_k doubles, mu: 2 doubles.
+int pearson_two_pass(const float* A, const float* B, int64_t n_or_k, int64_t ld, const int32_t* idx,
+                     double* out, double* part, double* mu, hipStream_t st) {
+  const int64_t n = n_or_k;
+  const double M = (double)pairs_of(n);
+  for (int stage = 0; stage < 2; ++stage) {
+    if (idx)
+      k_pearson_rows<true><<<(unsigned)n, 256, 0, st>>>(A, B, n, ld, idx, stage ? mu : nullptr, part);
+    else
+      k_pearson_rows<false><<<(unsigned)n, 256, 0, st>>>(A, B, n, ld, nullptr, stage ? mu : nullptr, part);
+    VR_CHECK_LAUNCH();
+    k_pearson_reduce<<<1, 256, 0, st>>>(part, n, mu, out, stage, M);
+    VR_CHECK_LAUNCH();
+  }
+  return VR_OK;
+}
+
 }  // namespace vr
 
 using namespace vr;
@@ -108,15 +141,34 @@ int vr_pearson_triu_f32(const float* A, const float* B, int64_t n, int64_t ld, d
   Carver c(ws);
   double* part = c.take<double>((size_t)n * 5);
   double* mu = c.take<double>(2);
-  k_pearson_rows<<<(unsigned)n, 256, 0, st>>>(A, B, n, ld, nullptr, part);
-  VR_CHECK_LAUNCH();
-  k_pearson_reduce<<<1, 256, 0, st>>>(part, n, mu, out, 0, (double)M);
-  VR_CHECK_LAUNCH();
-  k_pearson_rows<<<(unsigned)n, 256, 0, st>>>(A, B, n, ld, mu, part);
-  VR_CHECK_LAUNCH();
-  k_pearson_reduce<<<1, 256, 0, st>>>(part, n, mu, out, 1, (double)M);
-  VR_CHECK_LAUNCH();
-  return VR_OK;
+  return pearson_two_pass(A, B, n, ld, nullptr, out, part, mu, st);
+}
+
+size_t vr_pearson_triu_subset_workspace(int64_t k) { return vr_pearson_triu_workspace(k); }
+
+int vr_pearson_triu_subset_f32(const float* A, const float* B, int64_t n, int64_t ld,
+                               const int32_t* idx, int64_t k, double* out, void* ws,
+                               size_t ws_bytes, void* stream) {
+  clear_error();
+  VR_REQUIRE(n >= 0 && ld >= n && k >= 0 && k <= n && out != nullptr,
+             "vr_pearson_triu_subset_f32: bad arguments");
+  const size_t need = vr_pearson_triu_subset_workspace(k);
+  if (ws_bytes < need || ws == nullptr) {
+    set_error("vr_pearson_triu_subset_f32: workspace %zu < %zu", ws_bytes, need);
+    return VR_EWORKSPACE;
+  }
+  hipStream_t st = as_stream(stream);
+  if (pairs_of(k) < 2) {
+    const double nan = std::nan("");
+    VR_CHECK_HIP(hipMemcpyAsync(out, &nan, sizeof(double), hipMemcpyHostToDevice, st));
+    VR_CHECK_HIP(hipStreamSynchronize(st));
+    return VR_OK;
+  }
+  VR_REQUIRE(A != nullptr && B != nullptr && idx != nullptr, "vr_pearson_triu_subset_f32: null pointer");
+  Carver c(ws);
+  double* part = c.take<double>((size_t)k * 5);
+  double* mu = c.take<double>(2);
+  return pearson_two_pass(A, B, k, ld, idx, out, part, mu, st);
 }
 
 }  // extern "C"

@@ -232,11 +232,13 @@ def _score(best_layer, model_rdms, model_plans, neural_rdm, method, bootstrap, n
             model_plans[best_layer], RankPlan(neural_rdm), n_bootstrap=n_bootstrap, seed=42,
             method=method)
         boot_list = scores.tolist()
+    elif bootstrap and method == "pearson":  # no rank plan: the engine takes the RDMs
+        point, scores, ci_low, ci_high = bootstrap_rsa(
+            model_rdms[best_layer], neural_rdm, n_bootstrap=n_bootstrap, seed=42, method=method)
+        boot_list = scores.tolist()
     else:
         point = compute_rdm_correlation(model_rdms[best_layer], neural_rdm,
                                         correlation=method.capitalize())
-        if bootstrap:  # the valid compare methods (utils.py) all have an engine
-            raise NotImplementedError(f"bootstrap with compare_method='{method}'")
     msg = f"    subj {subj} | {method.capitalize():<10}| {best_layer} = {point:.4f}"
     if bootstrap:
         msg += f"  [95% CI: {ci_low:.4f}, {ci_high:.4f}]"
