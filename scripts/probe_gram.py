@@ -2,7 +2,7 @@
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-if os.environ.get("ALT_LIB"):  # another library build (scripts/build_alt.sh)
+if os.environ.get("ALT_LIB"):  # another library build (A/B)
     import visreps_amd._lib as _L
     _L.LIB_PATH = os.environ["ALT_LIB"]
 from visreps_amd.analysis import rsa as R

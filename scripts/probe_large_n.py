@@ -4,17 +4,13 @@
 Modes (one line each, ms per unit = HIP-event time of the calls / 12 units):
   grid     the region-fused call (bootstrap_spearman_grid; masks in LDS up to 20,352, else L2)
   region   one joined multi call per region (VISREPS_ENGINE_GRID path off: k_rankB per unit)
-and every score of `grid` is compared with `region` (bit-equal). ALT_LIB=path selects another
-library build (e.g. the prefetching walk with L2 masks, -DVR_XW_L2=1). SIZES=12000,20500."""
+and every score of `grid` is compared with `region` (bit-equal). SIZES=12000,20500."""
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
-if os.environ.get("ALT_LIB"):
-    import visreps_amd._lib as _L
-    _L.LIB_PATH = os.environ["ALT_LIB"]
 from visreps_amd import _lib
 from visreps_amd.analysis import rsa as R
 from visreps_amd.analysis._random import bootstrap_indices

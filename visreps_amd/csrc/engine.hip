@@ -40,10 +40,7 @@
 
 namespace vr {
 
-#ifndef VR_ENG_THREADS
-#define VR_ENG_THREADS 1024
-#endif
-constexpr int ENG_THREADS = VR_ENG_THREADS;  // waves per workgroup share one LDS mask table
+constexpr int ENG_THREADS = 1024;  // waves per workgroup share one LDS mask table
 constexpr int WAVES_PER_WG = ENG_THREADS / 64;
 constexpr int SCAN_SEGS = 256;     // segments per block in the segment scans / final fold
 
@@ -62,25 +59,6 @@ constexpr int SCAN_SEGS = 256;     // segments per block in the segment scans / 
 // ---------------------------------------------------------------------------------
 constexpr int EST_NC = 256;
 constexpr int EST_STEP_BITS = 12;  // interpolation steps per interval: 2^12
-#ifndef VR_EST_CHECK
-#define VR_EST_CHECK 1  // 0: timing probe only (no A-side recoverability checks: unsafe)
-#endif
-// Timing probes (wrong scores; never in the default build; profiles/r3_engine_probes.log):
-// VR_PROBE_WB replaces k_rankB's window mask lookups and transposes by a constant pattern,
-// VR_PROBE_ACC 1-3 strip its singleton accumulation (no 64-bit multiply / no St / one
-// 32-bit add), VR_PROBE_STW gives k_rankA one 4-byte store per two singleton rows.
-#ifndef VR_PROBE_STW
-#define VR_PROBE_STW 0  // k_rankA timing probe: half as many (4-byte) singleton stores
-#endif
-#ifndef VR_PROBE_WB
-#define VR_PROBE_WB 0
-#endif
-#ifndef VR_PROBE_WBA
-#define VR_PROBE_WBA 0  // the same for k_rankA
-#endif
-#ifndef VR_PROBE_ACC
-#define VR_PROBE_ACC 0
-#endif
 static std::atomic<int64_t> g_est_reruns{0};      // passes re-run in the exact form (vr_engine_est_reruns)
 static std::atomic<int64_t> g_est_predicted{0};   // calls sent to the exact form before any EST pass (vr_engine_est_predicted)
 static std::atomic<int64_t> g_est_tail_flags{0};  // of those, flagged by the tail invariants alone (vr_engine_est_tail_flags)
@@ -135,12 +113,10 @@ static int env_int(const char* name, int dflt) {
   return e && *e ? atoi(e) : dflt;
 }
 
-#ifndef VR_SEGS_PER_WAVE
-#define VR_SEGS_PER_WAVE 4  // most EST A-side segments per resident wave (workspace bound)
-#endif
+constexpr int SEGS_PER_WAVE = 4;  // most EST A-side segments per resident wave (workspace bound)
 // EST B walks take segments of >= 256 positions from a work queue, one per resident wave;
 // the A side cuts each of them into est_ratioA (VISREPS_ENGINE_SEGS_A, default and most
-// VR_SEGS_PER_WAVE) for its own queue (k_rankA; k_countA takes them round-robin).
+// SEGS_PER_WAVE) for its own queue (k_rankA; k_countA takes them round-robin).
 static uint32_t est_segments(int64_t M, int est_nwaves) {
   const int64_t by_len = (M + 255) / 256;
   return (uint32_t)std::max<int64_t>(1, std::min<int64_t>(by_len, (int64_t)est_nwaves));
@@ -180,7 +156,7 @@ static EngineCfg engine_cfg(int64_t n, int mode = 0) {
   c.est_grid = c.est_lds ? num_cus() * est_wg : c.grid;
   c.est_nwaves = c.est_grid * WAVES_PER_WG;
   c.est_nseg = est_segments(M, c.est_nwaves);
-  c.est_ratioA = (uint32_t)std::max(1, std::min(VR_SEGS_PER_WAVE, env_int("VISREPS_ENGINE_SEGS_A", VR_SEGS_PER_WAVE)));
+  c.est_ratioA = (uint32_t)std::max(1, std::min(SEGS_PER_WAVE, env_int("VISREPS_ENGINE_SEGS_A", SEGS_PER_WAVE)));
   // A segments of >= 1024 positions: small triangles (phase 1's M ~ 5e5) keep one per B
   // segment, where thousands of one-window segments would queue on a single counter
   while (c.est_ratioA > 1 && (uint64_t)c.est_nseg * c.est_ratioA * 1024u > (uint64_t)M) --c.est_ratioA;
@@ -237,8 +213,8 @@ static EngineWs engine_layout(void* base, int64_t n, int lw, int nwaves, size_t*
                               bool slim = false) {
   const int64_t M = pairs_of(n);
   const size_t nch = plan_nchunks(M);
-  // A-side segment partials: up to VR_SEGS_PER_WAVE per wave (EST); B-side: one per wave
-  const size_t nsegmax = (size_t)nwaves * VR_SEGS_PER_WAVE;
+  // A-side segment partials: up to SEGS_PER_WAVE per wave (EST); B-side: one per wave
+  const size_t nsegmax = (size_t)nwaves * SEGS_PER_WAVE;
   const size_t nsb = scan_blocks((uint32_t)nsegmax);
   Carver c(base);
   EngineWs e;
@@ -389,15 +365,10 @@ __device__ inline void tie_add(uint64_t& t64, u128& tbig, uint32_t k) {
   }
 }
 
-#ifndef VR_TB_STORE_NT
-#define VR_TB_STORE_NT 1  // TB rows written with nontemporal stores (0: default policy, A/B)
-#endif
+// TB rows are written with nontemporal stores
 template <typename T>
 __device__ inline void tb_store(T v, T* p) {
-  if constexpr (VR_TB_STORE_NT)
-    __builtin_nontemporal_store(v, p);
-  else
-    *p = v;
+  __builtin_nontemporal_store(v, p);
 }
 
 // rows [r0, r0 + cnt) of TB get v in this lane's column: row addresses are wave-uniform
@@ -622,7 +593,7 @@ __global__ __launch_bounds__(ENG_THREADS, 8) void k_countA(
       uint32_t w0 = P0 & ~63u;
       uint32_t cd = (w0 + lane >= P0 && w0 + lane < P1) ? codes[w0 + lane] : 0u;
       for (; w0 < P1; w0 += 64) {
-        const uint64_t x = window_bits<VR_XPOSE_A>(m, cd, w0, P0, P1, lane, active);
+        const uint64_t x = window_bits<XPOSE_A>(m, cd, w0, P0, P1, lane, active);
         if (w0 + 64 < P1) {
           const uint32_t q = w0 + 64 + lane;
           cd = q < P1 ? codes[q] : 0u;
@@ -727,12 +698,12 @@ __device__ inline void store_rows_est(uint16_t* __restrict__ TB, uint32_t stride
                                       uint32_t cnt, int lane, uint32_t y, const EstLo& el, bool& bad) {
   if (cnt == 0) return;
   // a group inside one 64-position window is covered by that window's check (k_rankA)
-  if (VR_EST_CHECK && (r0 >> 6) != ((r0 + cnt - 1u) >> 6))
+  if ((r0 >> 6) != ((r0 + cnt - 1u) >> 6))
     bad |= est_bad(y, est_lo_t<EST>(el, r0, lane)) || est_bad(y, est_lo_t<EST>(el, r0 + cnt - 1u, lane));
   uint16_t* row = TB + (size_t)r0 * stride + lane;
   if constexpr (EST == 4) {  // lane 0 (the full set): y - d(r) per row, positive (est4_shift)
     const uint32_t l0 = 0u - (uint32_t)(lane == 0);
-    if (VR_EST_CHECK) bad |= lane == 0 && (int32_t)(y - est4_shift(el.Ru, r0 + cnt - 1u)) < 1;
+    bad |= lane == 0 && (int32_t)(y - est4_shift(el.Ru, r0 + cnt - 1u)) < 1;
     for (uint32_t i = 0; i < cnt; ++i, row += stride) tb_store((uint16_t)(y - (est4_shift(el.Ru, r0 + i) & l0)), row);
     return;
   }
@@ -752,7 +723,7 @@ template <int EST, typename RowT>
 __device__ inline void store_rows_tri(uint16_t* __restrict__ TB, uint32_t r0, uint32_t cnt, int lane,
                                       uint32_t y, const EstLo& el, bool& bad, RowT&& row_t) {
   if (cnt == 0) return;
-  if (VR_EST_CHECK && (r0 >> 6) != ((r0 + cnt - 1u) >> 6))
+  if ((r0 >> 6) != ((r0 + cnt - 1u) >> 6))
     bad |= est_bad(y, est_lo_t<EST>(el, r0, lane)) || est_bad(y, est_lo_t<EST>(el, r0 + cnt - 1u, lane));
   for (uint32_t i = 0; i < cnt; ++i) {
     const uint32_t r = r0 + i;
@@ -842,11 +813,7 @@ __global__ __launch_bounds__(ENG_THREADS, 8) void k_rankA(
           tg = tri_tag<EST>(el, w0 + (uint32_t)lane);
           wt = w0;
         }
-  #if VR_PROBE_WBA  // timing probe only (wrong scores): k_rankA without mask lookups / transposes
-        const uint64_t x = active ? (0xF7DFBEFDFBF7EFDFull ^ ((uint64_t)(cd & 7u) << 3)) : 0ull;
-  #else
-        const uint64_t x = window_bits<VR_XPOSE_A>(m, cd, w0, P0, P1, lane, active);
-  #endif
+        const uint64_t x = window_bits<XPOSE_A>(m, cd, w0, P0, P1, lane, active);
         uint64_t F = restrict_flags(((uint64_t)f1 << 32) | f0, w0, P0, P1);
         asm volatile("" ::"v"(x) : "memory");
         if constexpr (EST) {
@@ -854,10 +821,8 @@ __global__ __launch_bounds__(ENG_THREADS, 8) void k_rankA(
           // [Y0, Y0 + 128] (Y0 = y0 + 2 cw + 1: cw <= cgs <= ce <= cw + 64), and lo is monotone,
           // in [lo(w0), lo(w0 + 63)]: these two checks make all of them recoverable. Longer
           // groups are checked where they close.
-          if (VR_EST_CHECK) {
-            const uint32_t Y0 = y0 + 2u * cw + 1u;
-            bad |= est_bad(Y0, est_lo_t<EST>(el, w0 + 63u, lane)) || est_bad(Y0 + 128u, est_lo_t<EST>(el, w0, lane));
-          }
+          const uint32_t Y0 = y0 + 2u * cw + 1u;
+          bad |= est_bad(Y0, est_lo_t<EST>(el, w0 + 63u, lane)) || est_bad(Y0 + 128u, est_lo_t<EST>(el, w0, lane));
         }
         if (w0 + 64 < P1) {
           const uint32_t q = w0 + 64 + lane;
@@ -880,30 +845,18 @@ __global__ __launch_bounds__(ENG_THREADS, 8) void k_rankA(
                 t = v + bit;
               }
             } else {
-  #if VR_PROBE_STW  // timing probe only (wrong TB layout): one 4-byte store per two rows
-            uint32_t* row2 = reinterpret_cast<uint32_t*>(TB + (size_t)w0 * stride) + lane;
   #pragma unroll
-            for (int j = 0; j < 62; j += 2) {
-              const uint32_t b0 = (uint32_t)(x >> j) & 1u, b1 = (uint32_t)(x >> (j + 1)) & 1u;
-              const uint32_t v0 = t + b0, v1 = v0 + b0 + b1;
-              if (active) __builtin_nontemporal_store(v0 | (v1 << 16), row2 + (size_t)j * stride / 2);
-              t = v1 + b1;
-            }
-            if (active) tb_store((TBT)t, row + (size_t)62 * stride);
-  #else
-  #pragma unroll
-            for (int j = 0; j < 63; ++j) {
-              const uint32_t bit = (uint32_t)(x >> j) & 1u;
-              const uint32_t v = t + bit;
-              if constexpr (EST == 4) {  // lane 0: shifted (est4_shift; singletons: y - d >= 2)
-                const uint32_t sub = est4_shift(el.Ru, w0 + (uint32_t)j) & (0u - (uint32_t)(lane == 0));
-                if (active) tb_store((TBT)(v - sub), row + (size_t)j * stride);
-              } else {
-                if (active) tb_store((TBT)v, row + (size_t)j * stride);
+              for (int j = 0; j < 63; ++j) {
+                const uint32_t bit = (uint32_t)(x >> j) & 1u;
+                const uint32_t v = t + bit;
+                if constexpr (EST == 4) {  // lane 0: shifted (est4_shift; singletons: y - d >= 2)
+                  const uint32_t sub = est4_shift(el.Ru, w0 + (uint32_t)j) & (0u - (uint32_t)(lane == 0));
+                  if (active) tb_store((TBT)(v - sub), row + (size_t)j * stride);
+                } else {
+                  if (active) tb_store((TBT)v, row + (size_t)j * stride);
+                }
+                t = v + bit;
               }
-              t = v + bit;
-            }
-  #endif
             }
             gs = w0 + 63u;
             cgs = cw + popc64(x & lowmask(63));
@@ -1025,25 +978,10 @@ __global__ void k_add_base(const uint32_t* __restrict__ lpA, const uint32_t* __r
 // Loads only. Per window three coalesced rows (codes, posA, chunkA) fetched one window
 // ahead; per pair its TB row (HBM, random) and A-chunk base row (L2-resident), issued 16
 // pairs at a time.
-#ifndef VR_RANKB_MINW
-#define VR_RANKB_MINW 8  // waves per SIMD the B pass is compiled for (8: 64 VGPRs)
-#endif
-#ifndef VR_RANKB_EST_MINW
-#define VR_RANKB_EST_MINW 8  // EST B walk: 8 waves per SIMD (two 1024-thread workgroups per CU)
-#endif
-#ifndef VR_XW_SLO
-#define VR_XW_SLO 0  // EST 3 prefetching walk: 1 = low ends in SALU from the address readlane (A/B; spills SGPRs)
-#endif
-#ifndef VR_RANKB_PIPE
-#define VR_RANKB_PIPE 0  // 1: gather batch h+1 in flight while batch h is consumed
-#endif
+constexpr int RANKB_MINW = 8;      // waves per SIMD the B pass is compiled for (8: 64 VGPRs)
+constexpr int RANKB_EST_MINW = 8;  // EST B walk: 8 waves per SIMD (two 1024-thread workgroups per CU)
 constexpr int BB = 8;  // pairs per gather batch
-#ifndef VR_TB_CACHE
 #define VR_TB_CACHE " nt"  // TB rows are read once: streaming loads keep L2 for the baseA rows
-#endif
-#ifndef VR_PROBE_NO_BASEA
-#define VR_PROBE_NO_BASEA 0
-#endif
 
 // BB pairs' yA = 2 baseA[chunkA] + TB[posA] for this lane. The loads are issued in the
 // saddr form (wave-uniform 64-bit row address in SGPRs + 32-bit lane byte offset), which
@@ -1063,43 +1001,22 @@ __device__ inline void gather_issue(const TBT* __restrict__ TB, const uint32_t* 
       asm volatile("global_load_ushort %0, %1, %2" VR_TB_CACHE : "=v"(t[q]) : "v"(lane_bt), "s"(trow) : "memory");
     else
       asm volatile("global_load_dword %0, %1, %2" : "=v"(t[q]) : "v"(lane_bt), "s"(trow) : "memory");
-#if VR_PROBE_NO_BASEA  // timing probe only: wrong scores
-    b[q] = 0u;
-#else
     asm volatile("global_load_dword %0, %1, %2" : "=v"(b[q]) : "v"(lane_b4), "s"(brow) : "memory");
-#endif
   }
 }
 
-// wait until at most PENDING of this wave's loads are outstanding; ties t, b
-template <int PENDING>
+// wait for all of this wave's loads; ties t, b
 __device__ inline void gather_wait(uint32_t t[BB], uint32_t b[BB]) {
   static_assert(BB == 8, "the wait below names 16 registers");
-  static_assert(PENDING == 0 || PENDING == 2 * BB, "vmcnt immediate");
-  if constexpr (PENDING == 0)
-    asm volatile("s_waitcnt vmcnt(0)"
-                 : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]),
-                   "+v"(t[7]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(b[4]), "+v"(b[5]),
-                   "+v"(b[6]), "+v"(b[7])
-                 :
-                 : "memory");
-  else
-    asm volatile("s_waitcnt vmcnt(16)"
-                 : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]),
-                   "+v"(t[7]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(b[4]), "+v"(b[5]),
-                   "+v"(b[6]), "+v"(b[7])
-                 :
-                 : "memory");
+  asm volatile("s_waitcnt vmcnt(0)"
+               : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]),
+                 "+v"(t[7]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(b[4]), "+v"(b[5]),
+                 "+v"(b[6]), "+v"(b[7])
+               :
+               : "memory");
 }
 
-#ifndef VR_EST_BB
-#define VR_EST_BB 8  // EST: pairs per gather batch (8, 16 or 32 loads in flight per wave)
-#endif
-#ifndef VR_EST_ASM
-#define VR_EST_ASM 1  // 0: plain loads (the compiler places the waits)
-#endif
-constexpr int EBB = VR_EST_BB;
-static_assert(EBB == 4 || EBB == 8 || EBB == 16 || EBB == 32, "EST batch");
+constexpr int EBB = 8;  // EST: pairs per gather batch (8 loads in flight per wave and batch)
 
 // EST: EBB pairs' TB entries only (absolute doubled ranks modulo 2^16), same load form
 __device__ inline void gather_issue_t(const uint16_t* __restrict__ TB, uint32_t stride, uint32_t pa,
@@ -1107,101 +1024,18 @@ __device__ inline void gather_issue_t(const uint16_t* __restrict__ TB, uint32_t 
 #pragma unroll
   for (int q = 0; q < EBB; ++q) {
     const char* trow = reinterpret_cast<const char*>(TB) + (size_t)readlane_u32(pa, j0 + q) * (stride * 2);
-#if VR_XP & 16  // timing probe only (wrong scores): no TB row gathers, the row address stands in
-    asm volatile("v_xor_b32 %0, %1, %2" : "=v"(t[q]) : "v"(lane_bt), "s"((uint32_t)(uintptr_t)trow) : "memory");
-#else
     asm volatile("global_load_ushort %0, %1, %2" VR_TB_CACHE : "=v"(t[q]) : "v"(lane_bt), "s"(trow) : "memory");
-#endif
   }
 }
 
-// EST 3 prefetching walk: the same loads, and each pair's window low end L + (2 posA R >> 32)
-// computed in SALU from the row index the address already needed in an SGPR (one
-// v_readlane per pair instead of two: the walk is bound by its vector-instruction issue,
-// DESIGN.md §3.3)
-__device__ inline void gather_issue_tl(const uint16_t* __restrict__ TB, uint32_t stride, uint32_t pa,
-                                       uint32_t j0, uint32_t lane_bt, uint32_t t[EBB], uint32_t lo[EBB],
-                                       uint32_t Lu, uint32_t Ru) {
-#pragma unroll
-  for (int q = 0; q < EBB; ++q) {
-    const uint32_t r = readlane_u32(pa, j0 + q);
-    const char* trow = reinterpret_cast<const char*>(TB) + (size_t)r * (stride * 2);
-    lo[q] = Lu + __umulhi(r << 1, Ru);
-#if VR_XP & 16  // timing probe only (wrong scores): no TB row gathers, the row address stands in
-    asm volatile("v_xor_b32 %0, %1, %2" : "=v"(t[q]) : "v"(lane_bt), "s"((uint32_t)(uintptr_t)trow) : "memory");
-#else
-    asm volatile("global_load_ushort %0, %1, %2" VR_TB_CACHE : "=v"(t[q]) : "v"(lane_bt), "s"(trow) : "memory");
-#endif
-  }
-}
-
-// wait for all of this wave's loads; ties the EBB results (16 per asm statement: the first
-// waits, the others only tell the compiler the registers are defined from here on)
-__device__ inline void wait_tie16(uint32_t* t, bool wait) {
-  if (wait)
-    asm volatile("s_waitcnt vmcnt(0)"
-                 : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]),
-                   "+v"(t[7]), "+v"(t[8]), "+v"(t[9]), "+v"(t[10]), "+v"(t[11]), "+v"(t[12]), "+v"(t[13]),
-                   "+v"(t[14]), "+v"(t[15])
-                 :
-                 : "memory");
-  else
-    asm volatile(""
-                 : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]),
-                   "+v"(t[7]), "+v"(t[8]), "+v"(t[9]), "+v"(t[10]), "+v"(t[11]), "+v"(t[12]), "+v"(t[13]),
-                   "+v"(t[14]), "+v"(t[15])
-                 :
-                 : "memory");
-}
-
+// wait for all of this wave's loads; ties the EBB results
 __device__ inline void gather_wait_t(uint32_t t[EBB]) {
-  if constexpr (EBB == 4) {
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]) : : "memory");
-  } else if constexpr (EBB == 8) {
-    asm volatile("s_waitcnt vmcnt(0)"
-                 : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]),
-                   "+v"(t[7])
-                 :
-                 : "memory");
-  } else {
-#pragma unroll
-    for (int g = 0; g < EBB / 16; ++g) wait_tie16(t + 16 * g, g == 0);
-  }
-}
-
-#ifndef VR_EST_ASM
-#define VR_EST_ASM 1  // 0: plain loads (the compiler places the waits)
-#endif
-#ifndef VR_EST_D16
-#define VR_EST_D16 0  // 1: two pairs' u16 entries per VGPR (short_d16 / short_d16_hi loads)
-#endif
-
-// EST, d16: wait for all of this wave's loads; ties the EBB / 2 packed registers
-__device__ inline void gather_wait_t16(uint32_t p[EBB / 2]) {
-  if constexpr (EBB == 8) {
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(p[0]), "+v"(p[1]), "+v"(p[2]), "+v"(p[3]) : : "memory");
-  } else if constexpr (EBB == 16) {
-    asm volatile("s_waitcnt vmcnt(0)"
-                 : "+v"(p[0]), "+v"(p[1]), "+v"(p[2]), "+v"(p[3]), "+v"(p[4]), "+v"(p[5]), "+v"(p[6]),
-                   "+v"(p[7])
-                 :
-                 : "memory");
-  } else {
-    wait_tie16(p, true);
-  }
-}
-
-// EST, d16: pairs j0 + 2i and j0 + 2i + 1 land in the low / high half of t[i], so a batch
-// of EBB pairs in flight holds EBB / 2 VGPRs
-__device__ inline void gather_issue_t16(const uint16_t* __restrict__ TB, uint32_t stride, uint32_t pa,
-                                        uint32_t j0, uint32_t lane_bt, uint32_t t[EBB / 2]) {
-#pragma unroll
-  for (int q = 0; q < EBB / 2; ++q) {
-    const char* r0 = reinterpret_cast<const char*>(TB) + (size_t)readlane_u32(pa, j0 + 2 * q) * (stride * 2);
-    const char* r1 = reinterpret_cast<const char*>(TB) + (size_t)readlane_u32(pa, j0 + 2 * q + 1) * (stride * 2);
-    asm volatile("global_load_short_d16 %0, %1, %2" VR_TB_CACHE : "=v"(t[q]) : "v"(lane_bt), "s"(r0) : "memory");
-    asm volatile("global_load_short_d16_hi %0, %1, %2" VR_TB_CACHE : "+v"(t[q]) : "v"(lane_bt), "s"(r1) : "memory");
-  }
+  static_assert(EBB == 8, "the wait below names 8 registers");
+  asm volatile("s_waitcnt vmcnt(0)"
+               : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]),
+                 "+v"(t[7])
+               :
+               : "memory");
 }
 
 // EST: yA of the window's 64 pairs (TB row entry + the window low end), EBB pairs per
@@ -1213,10 +1047,7 @@ __device__ inline void gather_issue_t16(const uint16_t* __restrict__ TB, uint32_
 // can promise that: tests/test_isa_guard.py checks it on every build's code object
 // (control-flow dataflow over every k_rankB instantiation, and zero scratch for the
 // default forms). EPS = 1 waits for each batch right after issuing it.
-#ifndef VR_EST_PIPE
-#define VR_EST_PIPE 2  // EST: gather batches in flight per wave (software pipeline depth; 1 = none)
-#endif
-constexpr int EPS = VR_EST_PIPE;
+constexpr int EPS = 2;  // EST: gather batches in flight per wave (software pipeline depth; 1 = none)
 
 // B side: the window low end of pair j of the window (lane j of pa / la holds pair j). EST 3
 // and 4 read the join's precomputed value (EST 4's lane 0: 2 posA + 1 - 2^15).
@@ -1240,15 +1071,11 @@ __device__ inline uint32_t est_lo_b(const EstLo& el, uint32_t pa, uint32_t la, i
 // wait until at most N of this wave's loads are outstanding; ties the EBB registers t
 template <int N>
 __device__ inline void gather_wait_n(uint32_t* t) {
-  if constexpr (EBB == 4) {
-    asm volatile("s_waitcnt vmcnt(%4)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]) : "n"(N) : "memory");
-  } else {
-    static_assert(EBB == 8, "pipelined EST batches are 4 or 8 pairs");
-    asm volatile("s_waitcnt vmcnt(%8)"
-                 : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7])
-                 : "n"(N)
-                 : "memory");
-  }
+  static_assert(EBB == 8, "pipelined EST batches are 8 pairs");
+  asm volatile("s_waitcnt vmcnt(%8)"
+               : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7])
+               : "n"(N)
+               : "memory");
 }
 
 // Software-pipelined batch H of a window: batches H+1 .. H+EPS-1 are issued before it is
@@ -1272,7 +1099,7 @@ __device__ inline void pipe_batch(const uint16_t* __restrict__ TB, uint32_t stri
 template <int EST, typename Fn>
 __device__ inline void gather_window_est(const uint16_t* __restrict__ TB, uint32_t stride, const EstLo& el,
                                          uint32_t pa, uint32_t la, uint32_t lane_bt, int lane, Fn&& fn) {
-  if constexpr (EPS > 1 && !VR_EST_D16) {
+  if constexpr (EPS > 1) {
     // the walk is bound by the gathers' round trip: keep EPS batches in flight
     uint32_t t[EPS][EBB];
 #pragma unroll
@@ -1283,25 +1110,8 @@ __device__ inline void gather_window_est(const uint16_t* __restrict__ TB, uint32
 #pragma unroll
   for (int h = 0; h < 64 / EBB; ++h) {
     uint32_t t[EBB];
-    if constexpr (VR_EST_D16 && EBB >= 8) {
-      uint32_t p[EBB / 2];
-      gather_issue_t16(TB, stride, pa, h * EBB, lane_bt, p);
-      gather_wait_t16(p);
-#pragma unroll
-      for (int q = 0; q < EBB / 2; ++q) {
-        t[2 * q] = p[q];  // est_recover uses only the low 16 bits
-        t[2 * q + 1] = p[q] >> 16;
-      }
-    } else if constexpr (VR_EST_ASM) {
-      gather_issue_t(TB, stride, pa, h * EBB, lane_bt, t);
-      gather_wait_t(t);
-    } else {
-#pragma unroll
-      for (int q = 0; q < EBB; ++q) {
-        const char* row = reinterpret_cast<const char*>(TB) + (size_t)readlane_u32(pa, h * EBB + q) * (stride * 2u);
-        t[q] = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(row + lane_bt));
-      }
-    }
+    gather_issue_t(TB, stride, pa, h * EBB, lane_bt, t);
+    gather_wait_t(t);
 #pragma unroll
     for (int q = 0; q < EBB; ++q)  // EST 3: the join's precomputed low end (lane j = pair j)
       t[q] = est_recover(t[q], est_lo_b<EST>(el, pa, la, h * EBB + q, lane, t[q]));
@@ -1314,56 +1124,18 @@ template <typename TBT, typename Fn>
 __device__ inline void gather_window(const TBT* __restrict__ TB, const uint32_t* __restrict__ baseA,
                                      uint32_t stride, uint32_t pa, uint32_t ca, uint32_t lane_bt,
                                      uint32_t lane_b4, Fn&& fn) {
-  if constexpr (VR_RANKB_PIPE) {
-    uint32_t t[2][BB], b[2][BB];
-    gather_issue<TBT>(TB, baseA, stride, pa, ca, 0, lane_bt, lane_b4, t[0], b[0]);
 #pragma unroll
-    for (int h = 0; h < 64 / BB; ++h) {
-      const int cur = h & 1;
-      if (h + 1 < 64 / BB) {
-        gather_issue<TBT>(TB, baseA, stride, pa, ca, (h + 1) * BB, lane_bt, lane_b4, t[cur ^ 1], b[cur ^ 1]);
-        gather_wait<2 * BB>(t[cur], b[cur]);
-      } else {
-        gather_wait<0>(t[cur], b[cur]);
-      }
-      uint32_t ya[BB];
+  for (int h = 0; h < 64 / BB; ++h) {
+    uint32_t t[BB], b[BB], ya[BB];
+    gather_issue<TBT>(TB, baseA, stride, pa, ca, h * BB, lane_bt, lane_b4, t, b);
+    gather_wait(t, b);
 #pragma unroll
-      for (int q = 0; q < BB; ++q) ya[q] = 2u * b[cur][q] + t[cur][q];
-      fn(h, ya);
-    }
-  } else {
-#pragma unroll
-    for (int h = 0; h < 64 / BB; ++h) {
-      uint32_t t[BB], b[BB], ya[BB];
-      gather_issue<TBT>(TB, baseA, stride, pa, ca, h * BB, lane_bt, lane_b4, t, b);
-      gather_wait<0>(t, b);
-#pragma unroll
-      for (int q = 0; q < BB; ++q) ya[q] = 2u * b[q] + t[q];
-      fn(h, ya);
-    }
+    for (int q = 0; q < BB; ++q) ya[q] = 2u * b[q] + t[q];
+    fn(h, ya);
   }
 }
 
-#ifndef VR_XP
-#define VR_XP 0  // timing probes of the prefetching walk's per-pair work (bitmask; wrong scores)
-#endif
-#ifndef VR_TAIL_CHECK
-#define VR_TAIL_CHECK 1  // 0: probe builds only -- the tail invariants never flag
-#endif
-#ifndef VR_PROBE_WT
-#define VR_PROBE_WT 0  // timing probe: per-wave start / end clocks of the last k_rankB launch
-#endif
-#if VR_PROBE_WT
-__device__ uint64_t g_wt[2 * 16384];
-#endif
-#ifndef VR_XW_L2
-#define VR_XW_L2 1  // the prefetching walk also with masks from L2 (n > 10,176); 0: the per-window walk there
-#endif
-#ifndef VR_XWIN
-#define VR_XWIN 1  // EST 3 / 4 B walk: next window's streams and masks fetched inside the window (0: off)
-#endif
-
-// EST 3 / 4 B walk, prefetching form (VR_XWIN; the window low ends computed from the A
+// EST 3 / 4 B walk, prefetching form (the window low ends computed from the A
 // positions in scalar registers, not streamed): every vector-memory load of the walk is
 // issued from asm and retired by a counted asm `s_waitcnt vmcnt(N)`, so the compiler places
 // no vmcnt wait of its own: the next window's streams S (codes, A positions: 2 loads) and
@@ -1393,7 +1165,7 @@ __device__ inline void xw_ldm(const uint64_t* m, uint32_t code, uint64_t& a, uin
 // B side. Exact form: yA = 2 baseA[chunkA] + TB[posA] (two gathers per pair). EST form:
 // yA recovered from TB[posA] (absolute, modulo 2^16) and the LDS count table (one gather).
 template <bool LDS, bool FULL, typename TBT, bool BIGT, int EST>
-__global__ __launch_bounds__(ENG_THREADS, EST ? VR_RANKB_EST_MINW : VR_RANKB_MINW) void k_rankB(
+__global__ __launch_bounds__(ENG_THREADS, EST ? RANKB_EST_MINW : RANKB_MINW) void k_rankB(
     const uint32_t* __restrict__ codes, const uint32_t* __restrict__ gstart,
     const uint32_t* __restrict__ chunk_g, const uint32_t* __restrict__ gflag, uint32_t nchunks,
     const uint64_t* __restrict__ gmask, int64_t n, const TBT* __restrict__ TB, int lw,
@@ -1411,9 +1183,6 @@ __global__ __launch_bounds__(ENG_THREADS, EST ? VR_RANKB_EST_MINW : VR_RANKB_MIN
   const bool active = FULL || lane < lw;
   const uint32_t stride = FULL ? (uint32_t)LANES : (uint32_t)lw;
   const uint32_t wave = wave_uniform(blockIdx.x * WAVES_PER_WG + (threadIdx.x >> 6));
-#if VR_PROBE_WT
-  if (lane == 0 && wave < 16384u) g_wt[wave] = wall_clock64();
-#endif
   // One segment [P0, P1) of B positions (a B tie-group start each), partial sums at index
   // sidx. EST passes: segments of ~M / est_nseg positions (segpos, k_seg_table) taken from
   // a work queue until none is left, so waves that run slow take fewer of them and the
@@ -1440,11 +1209,10 @@ __global__ __launch_bounds__(ENG_THREADS, EST ? VR_RANKB_EST_MINW : VR_RANKB_MIN
       // EST 3 / 4 (small tie groups): the prefetching walk, which computes the window low
       // ends from the A positions (a join's streamed low ends, VISREPS_ENGINE_LO_JOIN=1, hold
       // the same values and are not read)
-      // (with masks from L2 -- n > 10,176 -- too, VR_XW_L2; round 5 restricted it to LDS masks
+      // (with masks from L2 -- n > 10,176 -- too; round 5 restricted it to LDS masks
       // after a MEMORY_APERTURE_VIOLATION, whose cause was a probe build's SGPR spill restored
       // by v_readlane right before the asm mask load that reads it: see xw_ldm)
-      constexpr bool XW = VR_XWIN && EST == 3 && !BIGT && (LDS || VR_XW_L2);
-      constexpr bool walked = XW;
+      constexpr bool XW = EST == 3 && !BIGT;
       if constexpr (XW) {
         static_assert(EBB == 8, "prefetching batches are 8 pairs");
         {
@@ -1459,7 +1227,7 @@ __global__ __launch_bounds__(ENG_THREADS, EST ? VR_RANKB_EST_MINW : VR_RANKB_MIN
           // inclusion bits of window wv from its two mask words per lane
           auto bits_of = [&](uint32_t wv, uint64_t ma, uint64_t mb) -> uint64_t {
             const uint32_t pos = wv + (uint32_t)lane;
-            const uint64_t v = transpose64<VR_XPOSE_B>((pos >= P0 && pos < P1) ? (ma & mb) : 0ull, lane);
+            const uint64_t v = transpose64<XPOSE_B>((pos >= P0 && pos < P1) ? (ma & mb) : 0ull, lane);
             return active ? v : 0ull;
           };
           uint32_t w = P0 & ~63u;
@@ -1473,7 +1241,7 @@ __global__ __launch_bounds__(ENG_THREADS, EST ? VR_RANKB_EST_MINW : VR_RANKB_MIN
             asm volatile("s_waitcnt vmcnt(0)" : "+v"(ma), "+v"(mb) : : "memory");
             x = bits_of(w, ma, mb);
           } else {
-            x = window_bits<VR_XPOSE_B>(m, cd, w, P0, P1, lane, active);
+            x = window_bits<XPOSE_B>(m, cd, w, P0, P1, lane, active);
           }
           // group-start flags of the window (scalar loads), fetched one window ahead
           uint32_t f0 = sload(gflag + (w >> 5)), f1 = sload(gflag + (w >> 5) + 1);
@@ -1488,25 +1256,18 @@ __global__ __launch_bounds__(ENG_THREADS, EST ? VR_RANKB_EST_MINW : VR_RANKB_MIN
             // the window's batch pipeline; proc(h, ya) consumes batch h's recovered A ranks
             // (issued inside each of its two instances: a load in flight across the branch into
             // them would be copied between registers before its wait)
-            // batch issue: the TB row gathers of pairs j0 .. j0 + 7 (and, VR_XW_SLO, their low ends)
-            auto issue = [&](uint32_t j0, uint32_t* t, uint32_t* lq) {
-  #if VR_XW_SLO
-              gather_issue_tl(TB16, stride, pa, j0, lane_bt, t, lq, el.Lu, el.Ru);
-  #else
-              (void)lq;
-              gather_issue_t(TB16, stride, pa, j0, lane_bt, t);
-  #endif
-            };
+            // batch issue: the TB row gathers of pairs j0 .. j0 + 7
+            auto issue = [&](uint32_t j0, uint32_t* t) { gather_issue_t(TB16, stride, pa, j0, lane_bt, t); };
             auto pipeline = [&](auto&& proc) {
               uint64_t ma = 0, mb = 0;
-              uint32_t t[2][EBB], lq[2][EBB];
+              uint32_t t[2][EBB];
               xw_ld2(codes + wn, posA_byB + wn, voff_of(wn), cdn, pan);  // S(w+1)
-              issue(0, t[0], lq[0]);
+              issue(0, t[0]);
   #pragma unroll
               for (int h = 0; h < 64 / EBB; ++h) {
                 uint32_t(&cur)[EBB] = t[h & 1];
                 if (h + 1 < 64 / EBB) {
-                  issue((h + 1) * EBB, t[(h + 1) & 1], lq[(h + 1) & 1]);
+                  issue((h + 1) * EBB, t[(h + 1) & 1]);
                   gather_wait_n<EBB>(cur);
                   if (h == 0) asm volatile("" : "+v"(cdn), "+v"(pan));  // S(w+1): older than G[0]
                   if constexpr (!LDS) {
@@ -1517,47 +1278,29 @@ __global__ __launch_bounds__(ENG_THREADS, EST ? VR_RANKB_EST_MINW : VR_RANKB_MIN
                       asm volatile("" : "+v"(ma), "+v"(mb));
                       xn = bits_of(wn, ma, mb);
                     } else {
-  #if VR_XP & 8  // timing probe only (wrong scores): the mask lookups without the 64 x 64 transpose
-                      const uint32_t pn = wn + (uint32_t)lane;
-                      xn = (active && pn >= P0 && pn < P1) ? (m[cdn >> 16] & m[cdn & 0xffffu]) : 0ull;
-  #else
-                      xn = window_bits<VR_XPOSE_B>(m, cdn, wn, P0, P1, lane, active);
-  #endif
+                      xn = window_bits<XPOSE_B>(m, cdn, wn, P0, P1, lane, active);
                     }
                   }
                 } else {
                   gather_wait_n<0>(cur);
                 }
-                proc(h, cur, lq[h & 1]);
+                proc(h, cur);
               }
             };
-  #if VR_XW_SLO
-            // pair j's window low end (gather_issue_tl: scalar, from its row index)
-            auto recover = [&](uint32_t v, uint32_t lo) -> uint32_t { return est_recover(v, lo); };
-  #else
             // the window low ends of the window's A positions, lane j = pair j (3 VALU ops)
             const uint32_t la = el.Lu + __umulhi(pa << 1, el.Ru);
             auto recover = [&](uint32_t v, uint32_t j) -> uint32_t { return est_recover(v, readlane_u32(la, j)); };
-  #endif
             auto fast_proc = [&](uint64_t& a64, uint32_t& c1) {
-              return [&](int h, uint32_t* cur, const uint32_t* lo) {
+              return [&](int h, uint32_t* cur) {
   #pragma unroll
                 for (int q = 0; q < EBB; ++q) {
                   const uint32_t j = h * EBB + q;
-                  const uint32_t y = recover(cur[q], VR_XW_SLO ? lo[q] : j);
+                  const uint32_t y = recover(cur[q], j);
                   const uint32_t mk = (uint32_t)((int32_t)((uint32_t)(x >> (j & 32u)) << (31u - (j & 31u))) >> 31);
                   const uint32_t yb = y & mk;
                   if (j < 63) {
-  #if VR_XP & 1  // timing probe only (wrong scores): no 64-bit multiply-add
-                    a64 = (a64 & ~0xffffffffull) | (uint32_t)((uint32_t)a64 + (yb ^ c1));
-  #else
                     a64 += (uint64_t)yb * c1;
-  #endif
-  #if VR_XP & 2  // timing probe only: no 64-bit running sum
-                    c1 ^= yb & 1u;
-  #else
                     St += yb;
-  #endif
                     c1 -= mk;
                   } else {
                     S = yb;
@@ -1566,11 +1309,11 @@ __global__ __launch_bounds__(ENG_THREADS, EST ? VR_RANKB_EST_MINW : VR_RANKB_MIN
                 }
               };
             };
-            auto slow_proc = [&](int h, uint32_t* cur, const uint32_t* lo) {
+            auto slow_proc = [&](int h, uint32_t* cur) {
   #pragma unroll
               for (int q = 0; q < EBB; ++q) {
                 const uint32_t j = h * EBB + q;
-                const uint32_t y = recover(cur[q], VR_XW_SLO ? lo[q] : j);
+                const uint32_t y = recover(cur[q], j);
                 if ((F >> j) & 1ull) close(cw + popc64(x & lowmask(j)));
                 S += ((x >> j) & 1ull) ? (uint64_t)y : 0ull;
               }
@@ -1619,17 +1362,13 @@ __global__ __launch_bounds__(ENG_THREADS, EST ? VR_RANKB_EST_MINW : VR_RANKB_MIN
         f1 = sload(gflag + (w >> 5) + 1);
       };
       uint32_t pa = 0, ca = 0, cd = 0, f0 = 0, f1 = 0;
-      if constexpr (!walked) fetch(w0, pa, ca, cd, f0, f1);
-      for (; !walked && w0 < P1; w0 += 64) {
+      if constexpr (!XW) fetch(w0, pa, ca, cd, f0, f1);
+      for (; !XW && w0 < P1; w0 += 64) {
         const uint32_t pa_c = pa, ca_c = ca;
         uint32_t lane_b4, lane_bt;  // opaque per window, so the base + lane sum is not hoisted
         asm("" : "=v"(lane_b4) : "0"((uint32_t)lane * 4u));
         asm("" : "=v"(lane_bt) : "0"((uint32_t)lane * (uint32_t)sizeof(TBT)));
-  #if VR_PROBE_WB  // timing probe only (wrong scores): no mask lookups, no transpose
-        const uint64_t x = active ? (0xF7DFBEFDFBF7EFDFull ^ ((uint64_t)(cd & 7u) << 3)) : 0ull;
-  #else
-        const uint64_t x = window_bits<VR_XPOSE_B>(m, cd, w0, P0, P1, lane, active);
-  #endif
+        const uint64_t x = window_bits<XPOSE_B>(m, cd, w0, P0, P1, lane, active);
         const uint64_t F = restrict_flags(((uint64_t)f1 << 32) | f0, w0, P0, P1);
         if (w0 + 64 < P1) fetch(w0 + 64, pa, ca, cd, f0, f1);
         auto gather = [&](auto&& fn) {
@@ -1656,20 +1395,9 @@ __global__ __launch_bounds__(ENG_THREADS, EST ? VR_RANKB_EST_MINW : VR_RANKB_MIN
               const uint32_t m = (uint32_t)((int32_t)((uint32_t)(x >> (j & 32u)) << (31u - (j & 31u))) >> 31);
               const uint32_t yb = ya[q] & m;  // x is 0 on inactive lanes
               if (j < 63) {
-  #if VR_PROBE_ACC == 1
-                a64 += yb ^ c1;
-                St += yb;
-                c1 -= m;
-  #elif VR_PROBE_ACC == 2
-                a64 += yb ^ c1;
-                c1 -= m;
-  #elif VR_PROBE_ACC == 3
-                c1 += yb;
-  #else
                 a64 += (uint64_t)yb * c1;
                 St += yb;
                 c1 -= m;
-  #endif
               } else {
                 S = yb;
                 cgs = c1 - 1u;
@@ -1711,9 +1439,6 @@ __global__ __launch_bounds__(ENG_THREADS, EST ? VR_RANKB_EST_MINW : VR_RANKB_MIN
     const bool any = sg.c0 < sg.c1;
     walk_segment(wave, any ? chunk_start(gstart, chunk_g, sg.c0) : 0u, any ? chunk_start(gstart, chunk_g, sg.c1) : 0u);
   }
-#if VR_PROBE_WT
-  if (lane == 0 && wave < 16384u) g_wt[16384u + wave] = wall_clock64();
-#endif
 }
 
 // ---------------------------------------------------------------------------------
@@ -1736,24 +1461,14 @@ struct GridB {
   uint32_t* seg_tot[4];      // unit (j, region) segment partials (k_tail_part's inputs)
   uint64_t* seg_part[4];
 };
-#ifndef VR_GRID_NB
-#define VR_GRID_NB 4  // pairs per gather batch (x R regions loads in flight, two batches)
-#endif
-#ifndef VR_GRID_NT
-#define VR_GRID_NT 1  // TB rows read with nontemporal loads (each is read once per pass and region)
-#endif
-#ifndef VR_GRID_MASKMUL
-#define VR_GRID_MASKMUL 0  // 1: mask the shared multipliers instead of each region's rank (A/B)
-#endif
-#ifndef VR_GRID_MINW
-#define VR_GRID_MINW 4  // waves per SIMD the grid walk is compiled for (4: 128 VGPRs)
-#endif
+constexpr int GRID_NB = 4;    // pairs per gather batch (x R regions loads in flight, two batches)
+constexpr int GRID_MINW = 4;  // waves per SIMD the grid walk is compiled for (4: 128 VGPRs)
 template <int R, bool LDS>
-__global__ __launch_bounds__(ENG_THREADS, VR_GRID_MINW) void k_rankB_grid(
+__global__ __launch_bounds__(ENG_THREADS, GRID_MINW) void k_rankB_grid(
     const uint32_t* __restrict__ codes, const uint32_t* __restrict__ gflag, const uint64_t* __restrict__ gmask,
     int64_t n, GridB g, uint32_t nseg, const uint2* __restrict__ ftab, const uint32_t* __restrict__ segpos,
     uint32_t* __restrict__ queue) {
-  constexpr int NB = VR_GRID_NB;
+  constexpr int NB = GRID_NB;
   static_assert(64 % NB == 0, "batch");
   extern __shared__ uint64_t smask[];
   const uint64_t* m = stage_masks<LDS>(gmask, n, smask);
@@ -1793,20 +1508,17 @@ __global__ __launch_bounds__(ENG_THREADS, VR_GRID_MINW) void k_rankB_grid(
           pa[r] = valid ? g.posA[r][pos] : 0u;
           la[r] = Lu + __umulhi(pa[r] << 1, Ru);
         }
-        const uint64_t x = window_bits<VR_XPOSE_B>(m, cd, w0, P0, P1, lane, true);
+        const uint64_t x = window_bits<XPOSE_B>(m, cd, w0, P0, P1, lane, true);
         const uint64_t F =
             restrict_flags(((uint64_t)sload(gflag + (w0 >> 5) + 1) << 32) | sload(gflag + (w0 >> 5)), w0, P0, P1);
         // batch h's TB entries, t[r][q] = region r's row of pair h NB + q, lane's subset
+        // (nontemporal loads: each row is read once per pass and region)
         auto issue = [&](int h, uint32_t (&t)[R][NB]) {
 #pragma unroll
           for (int q = 0; q < NB; ++q)
 #pragma unroll
             for (int r = 0; r < R; ++r)
-#if VR_GRID_NT
               t[r][q] = __builtin_nontemporal_load(g.TB[r] + (size_t)readlane_u32(pa[r], h * NB + q) * LANES + lane_off);
-#else
-              t[r][q] = g.TB[r][(size_t)readlane_u32(pa[r], h * NB + q) * LANES + lane_off];
-#endif
         };
         uint32_t tb[2][R][NB];
         if (F == ~0ull) {  // every position starts a group (k_rankB's per-window form explains)
@@ -1823,23 +1535,13 @@ __global__ __launch_bounds__(ENG_THREADS, VR_GRID_MINW) void k_rankB_grid(
             for (int q = 0; q < NB; ++q) {
               const uint32_t j = h * NB + q;
               const uint32_t mk = (uint32_t)((int32_t)((uint32_t)(x >> (j & 32u)) << (31u - (j & 31u))) >> 31);
-#if VR_GRID_MASKMUL
-              // the inclusion mask on the shared multipliers: c1 & mk and mk & 1 (two 64-bit
-              // multiply-adds per region, no per-region mask)
-              const uint32_t c1m = c1 & mk, bit = mk & 1u;
-#endif
 #pragma unroll
               for (int r = 0; r < R; ++r) {
                 const uint32_t y = est_recover(tb[h & 1][r][q], readlane_u32(la[r], j));
                 if (j < 63) {
-#if VR_GRID_MASKMUL
-                  a64[r] += (uint64_t)y * c1m;
-                  St[r] += (uint64_t)y * bit;
-#else
                   const uint32_t yb = y & mk;
                   a64[r] += (uint64_t)yb * c1;
                   St[r] += yb;
-#endif
                 } else {
                   S[r] = y & mk;
                 }
@@ -1904,9 +1606,8 @@ struct GridX {
   uint32_t* seg_tot[4];
   uint64_t* seg_part[4];
 };
-#ifndef VR_GRIDX_NB
-#define VR_GRIDX_NB 2  // pairs per gather batch (x R regions x 2 loads in flight, two batches);
-#endif                 // 1 at R = 4, whose 2-pair batches do not fit 128 VGPRs
+constexpr int GRIDX_NB = 2;  // pairs per gather batch (x R regions x 2 loads in flight, two batches);
+                             // 1 at R = 4, whose 2-pair batches do not fit 128 VGPRs
 // chunk of A position pa: q = pa / L from the reciprocal Lm = floor(2^32 / L) (q is exact or
 // one low), then back over chunk starts above pa (group-aligned chunks start at or after c L)
 __device__ inline uint32_t a_chunk(uint32_t pa, const uint32_t* __restrict__ cst, uint32_t L, uint32_t Lm,
@@ -1918,11 +1619,11 @@ __device__ inline uint32_t a_chunk(uint32_t pa, const uint32_t* __restrict__ cst
   return q;
 }
 template <int R, bool LDS>
-__global__ __launch_bounds__(ENG_THREADS, VR_GRID_MINW) void k_rankB_gridx(
+__global__ __launch_bounds__(ENG_THREADS, GRID_MINW) void k_rankB_gridx(
     const uint32_t* __restrict__ codes, const uint32_t* __restrict__ gflag, const uint64_t* __restrict__ gmask,
     int64_t n, GridX g, uint32_t nseg, uint32_t L, uint32_t Lm, uint32_t nch, const uint32_t* __restrict__ segpos,
     uint32_t* __restrict__ queue) {
-  constexpr int NB = R >= 4 ? 1 : VR_GRIDX_NB;
+  constexpr int NB = R >= 4 ? 1 : GRIDX_NB;
   static_assert(64 % NB == 0, "batch");
   extern __shared__ uint64_t smask[];
   const uint64_t* m = stage_masks<LDS>(gmask, n, smask);
@@ -1961,7 +1662,7 @@ __global__ __launch_bounds__(ENG_THREADS, VR_GRID_MINW) void k_rankB_gridx(
           pa[r] = valid ? g.posA[r][pos] : 0u;
           ca[r] = a_chunk(pa[r], g.cst[r], L, Lm, nch);
         }
-        const uint64_t x = window_bits<VR_XPOSE_B>(m, cd, w0, P0, P1, lane, true);
+        const uint64_t x = window_bits<XPOSE_B>(m, cd, w0, P0, P1, lane, true);
         const uint64_t F =
             restrict_flags(((uint64_t)sload(gflag + (w0 >> 5) + 1) << 32) | sload(gflag + (w0 >> 5)), w0, P0, P1);
         // batch h's rows, t / b[r][q] = region r's TB entry / chunk base of pair h NB + q
@@ -2288,7 +1989,7 @@ __global__ void k_tail_top(const uint64_t* __restrict__ fpart0, uint32_t nblk,
   const bool broken = lane < nl && !forced_nan &&
                       (P != (uint64_t)totA[lane] || Ssum != (uint64_t)totA[lane] * ((uint64_t)totA[lane] + 1u));
   // bit 1 (the A walk's window checks set bit 0); benign race: every writer stores old | 2
-  if (VR_TAIL_CHECK && __ballot(broken) != 0 && lane == 0) *viol |= 2u;
+  if (__ballot(broken) != 0 && lane == 0) *viol |= 2u;
   if (lane >= nl) return;
   const u128 Mp = totA[lane];
   const u128 mu = Mp * (Mp + 1) * (Mp + 1);
@@ -2662,7 +2363,7 @@ static int run_engine_multi_impl(const PlanView& A, const PlanView* Bs, int64_t 
     if (lw == LANES && !cfg.use_lds && env_int("VISREPS_ENGINE_EST1_FALLBACK", 1) != 0) {
       EngineCfg c1 = engine_cfg(n, 1);
       c1.prejoined = cfg.prejoined;
-      if (c1.nwaves == cfg.nwaves && c1.est_nsegA <= (uint32_t)cfg.nwaves * VR_SEGS_PER_WAVE) {
+      if (c1.nwaves == cfg.nwaves && c1.est_nsegA <= (uint32_t)cfg.nwaves * SEGS_PER_WAVE) {
         g_est1_fallbacks.fetch_add(1);
         return run_engine_multi_impl(A, Bs, nb, n, idx, k, n_sets, full_first, scores, score_ld, joins, E, lw, c1,
                                      st);
@@ -3207,12 +2908,6 @@ int vr_test_engine_inject(int64_t pass) {
   g_test_inject.store(pass < 0 ? -1 : pass);
   return VR_OK;
 }
-#if VR_PROBE_WT
-// probe builds only: the wave start / end clocks (wall_clock64, 100 MHz) of the last k_rankB
-int vr_probe_wave_times(uint64_t* host) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_wt), sizeof(uint64_t) * 2 * 16384) == hipSuccess ? 0 : -1;
-}
-#endif
 
 size_t vr_bootstrap_workspace(int64_t n) {
   size_t b = 0;

@@ -16,10 +16,7 @@ int scan_exclusive_u32(const uint32_t* in, uint32_t* out, int64_t n, uint32_t* t
 
 // ---- LSD radix sort of (uint32 key, uint32 value) pairs (sort.hip) -----------------
 constexpr int RS_BS = 256;
-#ifndef VR_RS_IPT
-#define VR_RS_IPT 16
-#endif
-constexpr int RS_IPT = VR_RS_IPT;
+constexpr int RS_IPT = 16;
 constexpr int RS_TILE = RS_BS * RS_IPT;
 // One LSD pass (8-bit digit at `shift`) of (ki, vi) into (ko, vo): the building block of
 // radix_sort_kv, also the engine's partition of (B position, A position) pairs.

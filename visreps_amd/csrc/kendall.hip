@@ -52,9 +52,7 @@ struct KCfg {
   bool use_lds;
 };
 
-#ifndef VR_KW_MINB
-#define VR_KW_MINB 2  // walk blocks per CU the walks are compiled for (launch bounds)
-#endif
+constexpr int KW_MINB = 2;  // walk blocks per CU the walks are compiled for (launch bounds)
 static KCfg kendall_cfg(int64_t n) {
   KCfg c;
   const size_t need = (size_t)n * sizeof(uint64_t);
@@ -62,7 +60,7 @@ static KCfg kendall_cfg(int64_t n) {
   const char* e = getenv("VISREPS_KENDALL_MASKS");  // "global": masks from L2 (A/B timing)
   c.use_lds = need <= cap && !(e && strcmp(e, "global") == 0);
   const size_t per_block = std::max(c.use_lds ? need : (size_t)0, KW_STATIC_LDS);
-  const int per_cu = std::max<int>(1, std::min<int>(VR_KW_MINB, (int)(cap / per_block)));
+  const int per_cu = std::max<int>(1, std::min<int>(KW_MINB, (int)(cap / per_block)));
   c.grid = num_cus() * per_cu;
   c.nwaves = c.grid * KW_WAVES;
   c.lds = per_block;  // masks (LDS) and, after the walk, the partials
@@ -360,7 +358,7 @@ __device__ inline void kw_block_summary(const KSeg& a, bool seen, uint32_t incl,
 }
 
 template <bool LDS, bool TIE>
-__global__ __launch_bounds__(KW_THREADS, VR_KW_MINB) void k_kwalk(
+__global__ __launch_bounds__(KW_THREADS, KW_MINB) void k_kwalk(
     const uint32_t* __restrict__ codes, const uint32_t* __restrict__ sflag,
     const uint32_t* __restrict__ aux, int64_t M, const uint64_t* __restrict__ gmask, int64_t n,
     int nl, uint32_t nwaves, uint64_t* __restrict__ w_acc, uint64_t* __restrict__ w_g,
@@ -375,10 +373,6 @@ __global__ __launch_bounds__(KW_THREADS, VR_KW_MINB) void k_kwalk(
   KSeg a{0ull, 0u, 0u};
   bool seen = false;
   uint32_t incl = 0;
-#ifndef VR_KW_PAIR
-#define VR_KW_PAIR 1  // 1: two windows per trip (mask lookups, transposes and pair counts of both
-                      // first, straight-line, so their dependency chains interleave)
-#endif
   auto code_at = [&](uint32_t win) -> uint32_t {
     const uint32_t q = win * 64u + (uint32_t)lane;
     return q < (uint64_t)M ? codes[q] : 0u;
@@ -386,48 +380,32 @@ __global__ __launch_bounds__(KW_THREADS, VR_KW_MINB) void k_kwalk(
   auto bits_of = [&](uint32_t cd, uint32_t win) -> uint64_t {
     const uint32_t pos = win * 64u + (uint32_t)lane;
     const uint64_t mb = pos < (uint64_t)M ? (m[cd >> 16] & m[cd & 0xffffu]) : 0ull;
-    const uint64_t x = transpose64<VR_XPOSE_K>(mb, lane);
+    const uint64_t x = transpose64<XPOSE_K>(mb, lane);
     return active ? x : 0ull;
   };
   auto plane = [&](const uint32_t* f, uint32_t win) -> uint64_t {
     return ((uint64_t)sload(f + 2 * win + 1) << 32) | sload(f + 2 * win);
   };
-  if (VR_KW_PAIR) {
-    uint32_t c0 = 0, c1 = 0;
-    if (wb < we) c0 = code_at(wb);
-    if (wb + 1 < we) c1 = code_at(wb + 1);
-    for (uint32_t win = wb; win < we; win += 2) {
-      const bool two = win + 1 < we;  // wave-uniform
-      const uint32_t d0 = c0, d1 = c1;
-      if (win + 2 < we) c0 = code_at(win + 2);  // the next pair's codes, one trip ahead
-      if (win + 3 < we) c1 = code_at(win + 3);
-      const uint64_t x0 = bits_of(d0, win);
-      const uint64_t x1 = two ? bits_of(d1, win + 1) : 0ull;
-      const uint64_t S0 = plane(sflag, win), X0 = plane(aux, win);
-      const uint64_t S1 = plane(sflag, win + 1), X1 = plane(aux, win + 1);  // in the padded planes
-      const uint64_t o0 = x0 & X0, z0 = TIE ? o0 : (x0 & ~X0);
-      const uint64_t o1 = x1 & X1, z1 = TIE ? o1 : (x1 & ~X1);
-      const uint64_t i0 = kseg_inner<TIE>(o0, z0), i1 = kseg_inner<TIE>(o1, z1);
-      incl += popc64(x0) + popc64(x1);
-      kseg_window_inner<TIE>(o0, z0, S0, i0, a, seen);
-      if (two) kseg_window_inner<TIE>(o1, z1, S1, i1, a, seen);
-    }
-  } else {
-    uint32_t cd = 0;
-    if (wb < we) cd = code_at(wb);
-    for (uint32_t win = wb; win < we; ++win) {
-      const uint32_t d = cd;
-      if (win + 1 < we) cd = code_at(win + 1);  // next window's code, one ahead
-      const uint64_t x = bits_of(d, win);
-      const uint64_t S = plane(sflag, win), X = plane(aux, win);
-      incl += popc64(x);
-      if (TIE) {
-        const uint64_t o = x & X;
-        kseg_window<true>(o, o, S, a, seen);
-      } else {
-        kseg_window<false>(x & X, x & ~X, S, a, seen);
-      }
-    }
+  // two windows per trip (mask lookups, transposes and pair counts of both first,
+  // straight-line, so their dependency chains interleave)
+  uint32_t c0 = 0, c1 = 0;
+  if (wb < we) c0 = code_at(wb);
+  if (wb + 1 < we) c1 = code_at(wb + 1);
+  for (uint32_t win = wb; win < we; win += 2) {
+    const bool two = win + 1 < we;  // wave-uniform
+    const uint32_t d0 = c0, d1 = c1;
+    if (win + 2 < we) c0 = code_at(win + 2);  // the next pair's codes, one trip ahead
+    if (win + 3 < we) c1 = code_at(win + 3);
+    const uint64_t x0 = bits_of(d0, win);
+    const uint64_t x1 = two ? bits_of(d1, win + 1) : 0ull;
+    const uint64_t S0 = plane(sflag, win), X0 = plane(aux, win);
+    const uint64_t S1 = plane(sflag, win + 1), X1 = plane(aux, win + 1);  // in the padded planes
+    const uint64_t o0 = x0 & X0, z0 = TIE ? o0 : (x0 & ~X0);
+    const uint64_t o1 = x1 & X1, z1 = TIE ? o1 : (x1 & ~X1);
+    const uint64_t i0 = kseg_inner<TIE>(o0, z0), i1 = kseg_inner<TIE>(o1, z1);
+    incl += popc64(x0) + popc64(x1);
+    kseg_window_inner<TIE>(o0, z0, S0, i0, a, seen);
+    if (two) kseg_window_inner<TIE>(o1, z1, S1, i1, a, seen);
   }
   // The block's 16 wave ranges are consecutive: compose them here (affine carry maps, see
   // k_kfix) and write one summary per block, so the fix-up reads grid x 64 entries instead
@@ -440,7 +418,7 @@ __global__ __launch_bounds__(KW_THREADS, VR_KW_MINB) void k_kwalk(
 // pair codes (the x-lex order), so one walk shares the code loads, mask lookups and
 // transposes; three segment states, three block summaries (one k_kfix each).
 template <bool LDS>
-__global__ __launch_bounds__(KW_THREADS, VR_KW_MINB) void k_kwalk_top3(
+__global__ __launch_bounds__(KW_THREADS, KW_MINB) void k_kwalk_top3(
     const uint32_t* __restrict__ codes, const uint32_t* __restrict__ s0, const uint32_t* __restrict__ x0p,
     const uint32_t* __restrict__ s1, const uint32_t* __restrict__ x1p, const uint32_t* __restrict__ s2,
     const uint32_t* __restrict__ x2p, int64_t M, const uint64_t* __restrict__ gmask, int64_t n, int nl,
@@ -462,7 +440,7 @@ __global__ __launch_bounds__(KW_THREADS, VR_KW_MINB) void k_kwalk_top3(
   auto bits_of = [&](uint32_t cd, uint32_t win) -> uint64_t {
     const uint32_t pos = win * 64u + (uint32_t)lane;
     const uint64_t mb = pos < (uint64_t)M ? (m[cd >> 16] & m[cd & 0xffffu]) : 0ull;
-    const uint64_t x = transpose64<VR_XPOSE_K>(mb, lane);
+    const uint64_t x = transpose64<XPOSE_K>(mb, lane);
     return active ? x : 0ull;
   };
   auto plane = [&](const uint32_t* f, uint32_t win) -> uint64_t {

@@ -202,11 +202,8 @@ __global__ __launch_bounds__(KF_BS) void k_kf_lvl_count(const uint32_t* __restri
   if (threadIdx.x == 0) tile[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
-#ifndef VR_KF_LV_BS
-#define VR_KF_LV_BS 512
-#endif
 // the level kernels' blocks: LV_BS threads x LV_IPT consecutive elements = one KF_TILE
-constexpr int LV_BS = VR_KF_LV_BS;
+constexpr int LV_BS = 512;
 constexpr int LV_IPT = KF_TILE / LV_BS;
 static_assert(LV_BS * LV_IPT == KF_TILE, "level tile");
 

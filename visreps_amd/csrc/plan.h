@@ -9,13 +9,10 @@
 
 namespace vr {
 
-#ifndef VR_PLAN_L
-#define VR_PLAN_L 6144
-#endif
 // Target pairs per chunk: the per-wave work grain of the engine and the size of its
 // chunk-base table (nchunks x 256 B). 6144 gives one chunk per wave at N=10k on 256 CUs
 // (8192 waves) and a 2 MB table that stays in L2: 42.4 -> 36.3 ms per unit vs 2048.
-constexpr uint32_t PLAN_L = VR_PLAN_L;
+constexpr uint32_t PLAN_L = 6144;
 
 struct PlanHeader {
   int64_t n;

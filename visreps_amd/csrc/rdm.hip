@@ -964,16 +964,11 @@ __global__ __launch_bounds__(W_THREADS, 1) void k_gram3w(GramParams P) {
 // at chunk j ^ ((r >> 2) & 3), applied on the global source address, so a fragment read
 // (32 rows, one chunk) touches 16 distinct 16-B bank slots per 16 lanes.
 // ------------------------------------------------------------------------------------
-#ifndef VR_GRAM_PRIO
-#define VR_GRAM_PRIO 0  // 1: raise the wave priority over its MFMA block (A/B)
-#endif
 constexpr int P_PANEL = WT * 64;       // bytes of one panel sub-stage
 constexpr int P_SLOT = 2 * P_PANEL;    // A + B
-#ifndef VR_GRAM_SLOTS
-#define VR_GRAM_SLOTS 4  // sub-stage slots in LDS (5: 160 KB, one more sub-stage in flight; A/B)
-#endif
-constexpr int P_SLOTS = VR_GRAM_SLOTS;
+constexpr int P_SLOTS = 4;            // sub-stage slots in LDS
 constexpr int P_AHEAD = P_SLOTS - 1;  // iteration q issues sub-stage q + P_AHEAD
+static_assert(P_AHEAD == 3, "the counted waits of gram3p_step / gram3p_loop assume 4 slots");
 
 // this wave's two 1-KB pieces (16 rows each) of a panel sub-stage: rows [16 (2 w + i), +16)
 __device__ inline void p_issue(const GramParams& P, char* panel, int64_t row0, int q) {
@@ -989,19 +984,6 @@ __device__ inline void p_issue(const GramParams& P, char* panel, int64_t row0, i
     const char* src = reinterpret_cast<const char*>(P.planes) + ((row0 + r) * P.nstage + st) * 128 + off;
     __builtin_amdgcn_global_load_lds(src, panel + rbase * 64, 16, 0, 0);
   }
-}
-
-// one 1-KB piece (i = 0, 1) of p_issue
-__device__ inline void p_issue1(const GramParams& P, char* panel, int64_t row0, int q, int i) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int64_t st = q >> 1;
-  const int t = q & 1;
-  const int rbase = (wid * 2 + i) * 16;
-  const int r = rbase + (lane >> 2);
-  const int j = (lane & 3) ^ ((r >> 2) & 3);
-  const int off = ((j & 2) << 5) + 32 * t + ((j & 1) << 4);
-  const char* src = reinterpret_cast<const char*>(P.planes) + ((row0 + r) * P.nstage + st) * 128 + off;
-  __builtin_amdgcn_global_load_lds(src, panel + rbase * 64, 16, 0, 0);
 }
 
 __device__ inline bf16x8 p_frag(const char* panel, int row, int j) {
@@ -1034,41 +1016,7 @@ __device__ inline void p_read(const char* As, const char* Bs, PFrag& f) {
   }
 }
 
-#ifndef VR_GRAM_ILV
-#define VR_GRAM_ILV 0  // 1: the next sub-stage's LDS-DMA pieces issued between the MFMAs (A/B)
-#endif
-
-// p_mfma with callback g(k) after the 6k-th MFMA (k = 1..3): the same MFMA order
-template <typename G>
-__device__ inline void p_mfma_ilv(const PFrag& f, f32x16 (&acc)[4][2], G&& g) {
-  int c = 0;
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int nn = 0; nn < 2; ++nn) {
-      acc[m][nn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.aH[m], f.bH[nn], acc[m][nn], 0, 0, 0);
-      if (++c % 6 == 0) g(c / 6);
-    }
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int nn = 0; nn < 2; ++nn) {
-      acc[m][nn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.aH[m], f.bL[nn], acc[m][nn], 0, 0, 0);
-      if (++c % 6 == 0) g(c / 6);
-    }
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int nn = 0; nn < 2; ++nn) {
-      acc[m][nn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.aL[m], f.bH[nn], acc[m][nn], 0, 0, 0);
-      if (++c % 6 == 0) g(c / 6);
-    }
-}
-
 __device__ inline void p_mfma(const PFrag& f, f32x16 (&acc)[4][2]) {
-#if VR_GRAM_PRIO
-  __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
   for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -1084,9 +1032,6 @@ __device__ inline void p_mfma(const PFrag& f, f32x16 (&acc)[4][2]) {
 #pragma unroll
     for (int nn = 0; nn < 2; ++nn)
       acc[m][nn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.aL[m], f.bH[nn], acc[m][nn], 0, 0, 0);
-#if VR_GRAM_PRIO
-  __builtin_amdgcn_s_setprio(0);
-#endif
 }
 
 // Iteration q: sub-stage q's fragments are already in registers (cur); wait for this wave's
@@ -1099,14 +1044,12 @@ __device__ inline void gram3p_step(const GramParams& P, char* lds, int64_t row0,
   if (q + 1 < Q) {
     // this wave's loads of q+1 done; those of q+2 .. q+P_AHEAD-1 (issued) may stay in flight
     const int left = Q - 2 - q;
-    if (P_AHEAD >= 4 && left >= 2)
-      p_wait<(P_AHEAD >= 4 ? 2 : 1) * PER>();
-    else if (left >= 1)
+    if (left >= 1)
       p_wait<PER>();
     else
       p_wait<0>();
     __builtin_amdgcn_s_barrier();
-    if (!VR_GRAM_ILV && q + P_AHEAD < Q) {
+    if (q + P_AHEAD < Q) {
       char* slot = lds + ((q + P_AHEAD) % P_SLOTS) * P_SLOT;
       p_issue(P, slot, row0, q + P_AHEAD);
       if (!DIAG) p_issue(P, slot + P_PANEL, col0, q + P_AHEAD);
@@ -1114,28 +1057,7 @@ __device__ inline void gram3p_step(const GramParams& P, char* lds, int64_t row0,
     const char* As = lds + ((q + 1) % P_SLOTS) * P_SLOT;
     p_read(As, DIAG ? As : As + P_PANEL, nxt);
   }
-  if constexpr (VR_GRAM_ILV) {
-    // the slot of q+3 was last read in iteration q-1, before this iteration's barrier; the
-    // pieces are in flight before the next iteration's counted wait either way
-    static_assert(!VR_GRAM_ILV || P_AHEAD == 3, "interleaved issue: 4 slots");
-    const bool more = q + 3 < Q;
-    char* slot = lds + ((q + 3) % P_SLOTS) * P_SLOT;
-    p_mfma_ilv(cur, acc, [&](int k) {
-      if (!more) return;
-      if (DIAG) {
-        if (k <= 2) p_issue1(P, slot, row0, q + 3, k - 1);
-      } else {
-        if (k == 1) p_issue1(P, slot, row0, q + 3, 0);
-        if (k == 2) {
-          p_issue1(P, slot, row0, q + 3, 1);
-          p_issue1(P, slot + P_PANEL, col0, q + 3, 0);
-        }
-        if (k == 3) p_issue1(P, slot + P_PANEL, col0, q + 3, 1);
-      }
-    });
-  } else {
-    p_mfma(cur, acc);
-  }
+  p_mfma(cur, acc);
   // every P.flush stages (the same two-level sum as k_gram3w); its global loads and stores
   // drain this wave's loads in flight (the compiler waits vmcnt(0)): correct, and rare
   if (P.flush && (q & 1) && q + 1 < Q && ((q >> 1) + 1) % P.flush == 0) {
@@ -1156,9 +1078,7 @@ __device__ inline void gram3p_loop(const GramParams& P, char* lds, int64_t row0,
     if (!DIAG) p_issue(P, slot + P_PANEL, col0, q);
   }
   // sub-stage 0 landed: the loads of 1 .. P_AHEAD-1 may stay in flight
-  if (P_AHEAD >= 4 && Q > 3)
-    p_wait<(P_AHEAD >= 4 ? 3 : 2) * PER>();
-  else if (Q > 2)
+  if (Q > 2)
     p_wait<2 * PER>();
   else if (Q > 1)
     p_wait<PER>();
@@ -1355,16 +1275,10 @@ __device__ inline void e_read_b(const char* half, int r0, const ELane& o, EFragB
   }
 }
 
-#ifndef VR_E_PRIO
-#define VR_E_PRIO 0  // 1: s_setprio(1) over each phase's MFMAs (A/B)
-#endif
 // quadrant (MA, NB) of the wave's block: 4 x 2 tiles of 16 x 16, hh, hl, lh products
 // ONE (bf16 input, raw records of 64 k): hi = k 0..31, lo = k 32..63 of the stage, 2 products
 template <int MA, int NB, bool ONE>
 __device__ inline void e_mfma(const EFragA& a, const EFragB& b, f32x4 (&acc)[8][4]) {
-#if VR_E_PRIO
-  __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
   for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -1378,9 +1292,6 @@ __device__ inline void e_mfma(const EFragA& a, const EFragB& b, f32x4 (&acc)[8][
       for (int n = 0; n < 2; ++n)
         acc[MA * 4 + m][NB * 2 + n] =
             __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.lo[m], b.lo[n], acc[MA * 4 + m][NB * 2 + n], 0, 0, 0);
-#if VR_E_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
     return;
   }
 #pragma unroll
@@ -1395,9 +1306,6 @@ __device__ inline void e_mfma(const EFragA& a, const EFragB& b, f32x4 (&acc)[8][
     for (int n = 0; n < 2; ++n)
       acc[MA * 4 + m][NB * 2 + n] =
           __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.lo[m], b.hi[n], acc[MA * 4 + m][NB * 2 + n], 0, 0, 0);
-#if VR_E_PRIO
-  __builtin_amdgcn_s_setprio(0);
-#endif
 }
 
 // 16 x 16 C/D map: col = lane & 15, row = 4 (lane >> 4) + e. Flush buffer: the block's

@@ -3,27 +3,16 @@
 // scatter, where each 4096-element tile is first ordered by digit in LDS, then written
 // out digit-run by digit-run (coalesced). The in-tile order comes from wave ballots
 // (k_rs_scatter: each wave ranks its 1024 keys in rounds of 64 by the peer masks of
-// eight ballots, then per-wave digit totals place them); VR_RS_SPLIT8 builds the older
-// form, eight stable 1-bit splits over the tile.
+// eight ballots, then per-wave digit totals place them).
 // Used once per RDM to order its strict upper triangle by value (the rank plan).
 #include "internal.h"
 
 namespace vr {
 
-#ifndef VR_RS_XCD
-#define VR_RS_XCD 1
-#endif
-// Tile of this block. With VR_RS_XCD the blocks one XCD receives take consecutive tiles
-// (xcd_item), so the digit runs that neighbouring tiles write side by side meet in the
-// same L2 instead of in eight.
-__device__ inline int64_t rs_tile(int64_t nb) {
-#if VR_RS_XCD
-  return xcd_item(nb);
-#else
-  (void)nb;
-  return blockIdx.x;
-#endif
-}
+// Tile of this block. The blocks one XCD receives take consecutive tiles (xcd_item), so
+// the digit runs that neighbouring tiles write side by side meet in the same L2 instead
+// of in eight.
+__device__ inline int64_t rs_tile(int64_t nb) { return xcd_item(nb); }
 
 __global__ __launch_bounds__(RS_BS) void k_rs_hist(const uint32_t* __restrict__ keys,
                                                    int64_t n, int shift,
@@ -138,11 +127,6 @@ __global__ __launch_bounds__(256) void k_rs_colapply(uint32_t* __restrict__ h, i
   }
 }
 
-#ifndef VR_RS_SPLIT8
-#define VR_RS_SPLIT8 0
-#endif
-
-#if !VR_RS_SPLIT8
 // Each wave ranks its own 1024 consecutive keys in 16 rounds of 64 with no block barrier:
 // a key's rank among the same-digit keys of its round from the peer mask of eight
 // ballots, plus the wave's running count of that digit (wave-private LDS counters). The
@@ -236,86 +220,6 @@ __global__ __launch_bounds__(RS_BS) void k_rs_scatter(
     }
   }
 }
-#else
-template <bool KV = true>
-__global__ __launch_bounds__(RS_BS) void k_rs_scatter(
-    const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin,
-    uint32_t* __restrict__ kout, uint32_t* __restrict__ vout, int64_t n, int shift,
-    const uint32_t* __restrict__ offs, int64_t nb) {
-  constexpr int PADDED = RS_TILE + RS_TILE / 32;
-  __shared__ uint32_t sk[PADDED];
-  __shared__ uint32_t sv[PADDED];
-  __shared__ uint32_t cnt[256];
-  __shared__ uint32_t start[256];
-  __shared__ uint32_t scan_lds[RS_BS / 64 + 1];
-
-  const int t = threadIdx.x;
-  const int64_t tile = rs_tile(nb);
-  const int64_t base = tile * RS_TILE;
-  cnt[t] = 0;
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < RS_IPT; ++j) {
-    int p = j * RS_BS + t;
-    int64_t i = base + p;
-    uint32_t k = 0xFFFFFFFFu, v = 0;
-    if (i < n) {
-      k = kin[i];
-      if constexpr (KV) v = vin[i];
-      atomicAdd(&cnt[(k >> shift) & 255u], 1u);
-    }
-    sk[lds_pad(p)] = k;
-    sv[lds_pad(p)] = v;
-  }
-  __syncthreads();
-
-  // Stable local ordering by the 8 digit bits: 8 one-bit splits on the blocked layout
-  // (thread t owns positions 16t .. 16t+15). Padding keys (0xFFFFFFFF) stay last.
-  for (int bit = 0; bit < 8; ++bit) {
-    uint32_t kk[RS_IPT], vv[RS_IPT];
-    uint32_t zeros = 0;
-#pragma unroll
-    for (int j = 0; j < RS_IPT; ++j) {
-      kk[j] = sk[lds_pad(t * RS_IPT + j)];
-      vv[j] = sv[lds_pad(t * RS_IPT + j)];
-      zeros += ((kk[j] >> (shift + bit)) & 1u) ^ 1u;
-    }
-    uint32_t Z;
-    uint32_t Zt = block_exclusive_scan<RS_BS>(zeros, scan_lds, Z);  // ends with a barrier
-    uint32_t zb = 0;
-#pragma unroll
-    for (int j = 0; j < RS_IPT; ++j) {
-      uint32_t b = (kk[j] >> (shift + bit)) & 1u;
-      uint32_t idx = (uint32_t)(t * RS_IPT + j);
-      uint32_t pos = b ? (Z + idx - (Zt + zb)) : (Zt + zb);
-      zb += b ^ 1u;
-      sk[lds_pad((int)pos)] = kk[j];
-      sv[lds_pad((int)pos)] = vv[j];
-    }
-    __syncthreads();
-  }
-
-  // digit start offsets inside the tile (valid elements only)
-  {
-    uint32_t c = cnt[t], tot;
-    uint32_t s = block_exclusive_scan<RS_BS>(c, scan_lds, tot);
-    start[t] = s;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < RS_IPT; ++j) {
-    int s = j * RS_BS + t;
-    uint32_t k = sk[lds_pad(s)];
-    uint32_t d = (k >> shift) & 255u;
-    uint32_t r = (uint32_t)s - start[d];
-    if (r < cnt[d]) {
-      int64_t g = (int64_t)offs[tile * 256 + d] + r;
-      kout[g] = k;
-      if constexpr (KV) vout[g] = sv[lds_pad(s)];
-    }
-  }
-}
-#endif
 
 size_t radix_ws_elems(int64_t n) {
   const int64_t nb = (n + RS_TILE - 1) / RS_TILE;

@@ -18,10 +18,7 @@
 namespace vr {
 
 constexpr int SRP_T = 64;
-#ifndef VR_SRP_U
-#define VR_SRP_U 16
-#endif
-constexpr int SRP_U = VR_SRP_U;  // nonzeros per batch of row loads
+constexpr int SRP_U = 16;  // nonzeros per batch of row loads
 
 __global__ __launch_bounds__(256) void k_srp_transpose(const float* __restrict__ X, int64_t B,
                                                        int64_t D, int64_t ldx, int64_t Bp,

@@ -36,35 +36,20 @@ __device__ inline uint64_t shfl_xor64(uint64_t v, int m) {
   return ((uint64_t)hi << 32) | lo;
 }
 
-#ifndef VR_FAST_XOR
-#define VR_FAST_XOR 1  // lane exchanges of the transpose: 1: DPP (xor 1, 2), ds_swizzle (4, 8, 16), permlane32_swap (32);
-                       // 2: DPP for 4, 8 and permlane16_swap for 16 (more VALU: measured slower); 0: ds_bpermute
-#endif
-
 // v from lane (lane ^ W). W = 1, 2: DPP quad_perm on the VALU (no LDS-pipe round trip);
-// W = 4, 8, 16: ds_swizzle bit-mask mode (xor within 32 lanes, no address register);
+// W = 4, 8, 16: ds_swizzle bit-mask mode (xor within 32 lanes, no address register; DPP for
+// 4, 8 and permlane16_swap for 16 cost more VALU and measured slower);
 // W = 32: v_permlane32_swap (gfx950) of v with itself: afterwards the first result holds
 // [v(0..31), v(0..31)] and the second [v(32..63), v(32..63)] across the wave.
 template <int W>
 __device__ inline uint32_t xor_lane(uint32_t v, int lane) {
-  if constexpr (!VR_FAST_XOR) {
-    return (uint32_t)__shfl_xor((int)v, W);
-  } else if constexpr (W == 32) {
+  if constexpr (W == 32) {
     const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
     return lane < 32 ? r[1] : r[0];
   } else if constexpr (W == 1) {
     return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false);  // quad_perm [1,0,3,2]
   } else if constexpr (W == 2) {
     return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, false);  // quad_perm [2,3,0,1]
-  } else if constexpr (W == 4 && VR_FAST_XOR >= 2) {
-    // i ^ 4 = half-row mirror (7 - i in 8) of the quad mirror (3 - i in 4)
-    const int m = __builtin_amdgcn_mov_dpp((int)v, 0x1B, 0xF, 0xF, false);  // quad_perm [3,2,1,0]
-    return (uint32_t)__builtin_amdgcn_mov_dpp(m, 0x141, 0xF, 0xF, false);    // row_half_mirror
-  } else if constexpr (W == 8 && VR_FAST_XOR >= 2) {
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x128, 0xF, 0xF, false);  // row_ror:8
-  } else if constexpr (W == 16 && VR_FAST_XOR >= 2) {
-    const auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-    return (lane & 16) ? r[0] : r[1];
   } else {
     return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, (W << 10) | 0x1F);  // and 0x1f, xor W
   }
@@ -92,20 +77,15 @@ __device__ inline uint64_t transpose_stage(uint64_t x, int lane) {
 
 // Transpose forms (template argument XM of transpose64 / window_bits):
 //   1: the 64-bit stages above;
-//   2: half-word stages (one exchange, one per-lane rotate, one bit select per 32-bit half;
-//      the w = 32 stage one permlane32_swap), per-lane stage constants rebuilt per call;
-//   3: the same with the constants loop-invariant (the compiler keeps them in ~9 VGPRs).
-// Defaults per walk (A side: count and rank walks; B side: the rank walks at their VGPR
-// budget, where 2 measured no faster than 1; Kendall: the stream walks).
-#ifndef VR_XPOSE_A
-#define VR_XPOSE_A 3
-#endif
-#ifndef VR_XPOSE_B
-#define VR_XPOSE_B 1
-#endif
-#ifndef VR_XPOSE_K
-#define VR_XPOSE_K 3
-#endif
+//   3: half-word stages (one exchange, one per-lane rotate, one bit select per 32-bit half;
+//      the w = 32 stage one permlane32_swap), the per-lane stage constants loop-invariant
+//      (the compiler keeps them in ~9 VGPRs).
+// Form per walk (A side: count and rank walks; B side: the rank walks at their VGPR
+// budget, where the half-word stages with their constants rebuilt per call measured no
+// faster than 1; Kendall: the stream walks).
+constexpr int XPOSE_A = 3;
+constexpr int XPOSE_B = 1;
+constexpr int XPOSE_K = 3;
 
 // Stage ST >= 1 (w = 32 >> ST <= 16) on one 32-bit half: the stage's bit moves stay inside
 // each half. A lane with lane bit w clear keeps its K bits and takes the partner's K bits
@@ -130,7 +110,7 @@ __device__ inline void transpose_stage_h(uint32_t& lo, uint32_t& hi, int lane) {
 // on exit bit j of lane s is. Recursive block swap, 6 stages of one 64-bit exchange.
 template <int XM>
 __device__ inline uint64_t transpose64(uint64_t x, int lane) {
-  static_assert(XM >= 1 && XM <= 3, "transpose form");
+  static_assert(XM == 1 || XM == 3, "transpose form");
   if constexpr (XM == 1) {
     x = transpose_stage<0>(x, lane);
     x = transpose_stage<1>(x, lane);
@@ -139,7 +119,6 @@ __device__ inline uint64_t transpose64(uint64_t x, int lane) {
     x = transpose_stage<4>(x, lane);
     return transpose_stage<5>(x, lane);
   }
-  if constexpr (XM == 2) asm volatile("" : "+v"(lane));  // opaque per call: not loop-invariant
   uint32_t lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
   {  // w = 32: lanes 0-31 take lanes 32-63's low words as their high words and vice versa
     const auto r = __builtin_amdgcn_permlane32_swap(lo, hi, false, false);
@@ -152,22 +131,6 @@ __device__ inline uint64_t transpose64(uint64_t x, int lane) {
   transpose_stage_h<4>(lo, hi, lane);
   transpose_stage_h<5>(lo, hi, lane);
   return ((uint64_t)hi << 32) | lo;
-}
-
-// the round-1 form (every exchange a ds_bpermute): kept for reference timing
-__device__ inline uint64_t transpose64_bperm(uint64_t x, int lane) {
-  constexpr uint64_t K[6] = {0x00000000FFFFFFFFull, 0x0000FFFF0000FFFFull, 0x00FF00FF00FF00FFull,
-                             0x0F0F0F0F0F0F0F0Full, 0x3333333333333333ull, 0x5555555555555555ull};
-#pragma unroll
-  for (int st = 0; st < 6; ++st) {
-    const int w = 32 >> st;
-    const uint64_t p = shfl_xor64(x, w);
-    const uint64_t hi = (x & ~K[st]) | ((p & ~K[st]) >> w);  // lanes with bit w set
-    const uint64_t lo = (x & K[st]) | ((p & K[st]) << w);
-    const uint64_t sel = 0ull - (uint64_t)((lane >> (5 - st)) & 1);  // branch-free select
-    x = (hi & sel) | (lo & ~sel);
-  }
-  return x;
 }
 
 __host__ __device__ inline uint64_t lowmask(uint32_t b) { return b >= 64 ? ~0ull : ((1ull << b) - 1ull); }
