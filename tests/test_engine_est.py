@@ -4,7 +4,7 @@ form and the CPU oracle.
 EST keeps each pair's absolute doubled A rank modulo 2^16 and recovers it on the B side
 from an estimate of the included-pair count (EST 3, the default: one wave-uniform linear
 estimate, the pass holding the full set run exact; EST 1: an interpolated per-lane table in
-LDS; EST 2: a per-lane linear estimate); a pass whose ranks cannot be recovered is re-run
+LDS); a pass whose ranks cannot be recovered is re-run
 in the exact form. Both forms are exact integer arithmetic, so scores must agree bit for bit
 (VISREPS_ENGINE_EST=1 selects the EST form, =0 the exact form, for every pass;
 VISREPS_ENGINE_EST_MODE the estimate).
@@ -121,7 +121,7 @@ def test_est_giant_tie_groups_fall_back_to_exact(dev):
         assert abs(est[1 + s] - ref_s) <= 1e-12
 
 
-@pytest.mark.parametrize("mode", ["1", "2", "3"])
+@pytest.mark.parametrize("mode", ["1", "3"])
 def test_est_modes_equal_exact_form(dev, mode, monkeypatch):
     # every estimate form, a partial last pass (201 subsets: lanes 9..63 hold no subset)
     monkeypatch.setenv("VISREPS_ENGINE_EST_MODE", mode)
@@ -132,23 +132,6 @@ def test_est_modes_equal_exact_form(dev, mode, monkeypatch):
     r0 = int(lib().vr_engine_est_reruns())
     est = R.bootstrap_spearman_multi(neural, models, idx, full_first=True).cpu().numpy()
     assert int(lib().vr_engine_est_reruns()) == r0, "continuous RDMs must not need the exact re-run"
-    with exact_engine():
-        ref = R.bootstrap_spearman_multi(neural, models, idx, full_first=True).cpu().numpy()
-    assert np.array_equal(est, ref)
-
-
-@pytest.mark.parametrize("n,nb", [(2500, 200), (700, 64)])
-def test_triangle_order_form_equals_exact_form(dev, n, nb, monkeypatch):
-    # EST 5 / 6 (opt-in VISREPS_ENGINE_TRI=1): TB rows at triangle indices, 63 subsets per
-    # pass, lane 63 the tag; 201 / 65 draws leave partial last passes
-    monkeypatch.setenv("VISREPS_ENGINE_TRI", "1")
-    neural = R.RankPlan(_rdm(dev, n, 120, 31))
-    models = [R.RankPlan(_rdm(dev, n, 90, 32, relu=True)), R.RankPlan(_rdm(dev, n, 300, 33))]
-    idx = bootstrap_indices(42, n, int(0.9 * n), nb)
-    r0, t0 = int(lib().vr_engine_est_reruns()), int(lib().vr_engine_est_tail_flags())
-    est = R.bootstrap_spearman_multi(neural, models, idx, full_first=True).cpu().numpy()
-    assert int(lib().vr_engine_est_reruns()) == r0, "continuous RDMs must not need the exact re-run"
-    assert int(lib().vr_engine_est_tail_flags()) == t0
     with exact_engine():
         ref = R.bootstrap_spearman_multi(neural, models, idx, full_first=True).cpu().numpy()
     assert np.array_equal(est, ref)
@@ -314,13 +297,6 @@ def test_grid_equals_per_region_calls(dev, na):
     with exact_engine():  # the exact form runs the per-region calls
         ex = R.bootstrap_spearman_grid(neurals, models, idx, joins, full_first=True).cpu().numpy()
     assert np.array_equal(ex, got)
-    ktimer_enable(True)
-    with exact_engine(), _exact_grid():  # or region-fused (opt-in, k_rankB_gridx)
-        ex = R.bootstrap_spearman_grid(neurals, models, idx, joins, full_first=True).cpu().numpy()
-    gridx_launches = ktimer_read("k_rankB_gridx")[1]
-    ktimer_enable(False)
-    assert gridx_launches == 3 * len(models), "the exact grid walk: one launch per model plan and pass"
-    assert np.array_equal(ex, got)
 
 
 def test_grid_falls_back_on_a_structured_region(dev):
@@ -428,16 +404,6 @@ def test_grid_structured_region_leaves_the_others_fused(dev):
         assert np.array_equal(got[a], ref)
 
 
-class _exact_grid:
-    """Context: the region-fused exact walk (VISREPS_ENGINE_GRIDX=1, opt-in)."""
-
-    def __enter__(self):
-        os.environ["VISREPS_ENGINE_GRIDX"] = "1"
-
-    def __exit__(self, *a):
-        os.environ.pop("VISREPS_ENGINE_GRIDX", None)
-
-
 def _structured_rdm(dev, n, seed):
     g = torch.Generator(device=dev).manual_seed(seed)
     u = torch.empty(n, device=dev).exponential_(1.0, generator=g) ** 2
@@ -446,11 +412,10 @@ def _structured_rdm(dev, n, seed):
     return s + s.T
 
 
-def test_grid_structured_regions_walk_the_exact_grid(dev):
-    # regions whose estimate fails the up-front check go to the exact form; with
-    # the exact grid on, two or more of them walk it region-fused (k_rankB_gridx), the
-    # continuous ones stay in the EST grid, and every score equals the per-region calls (and
-    # the default, the structured regions' own exact calls)
+def test_grid_structured_regions_leave_and_the_others_stay_fused(dev):
+    # regions whose estimate fails the up-front check leave the fused set and
+    # go to the exact form on their own (two of them here), the continuous ones stay in the
+    # EST grid, and every score equals the per-region calls
     from visreps_amd._lib import ktimer_enable, ktimer_read
 
     n = 5000
@@ -462,31 +427,23 @@ def test_grid_structured_regions_walk_the_exact_grid(dev):
     joins = [sj.join(pm) for pm in models]
     p0, r0 = int(lib().vr_engine_est_predicted()), int(lib().vr_engine_est_reruns())
     ktimer_enable(True)
-    with _exact_grid():
-        got = R.bootstrap_spearman_grid(neurals, models, idx, joins, full_first=True).cpu().numpy()
+    got = R.bootstrap_spearman_grid(neurals, models, idx, joins, full_first=True).cpu().numpy()
     est_launches = ktimer_read("k_rankB_grid")[1]
-    gridx_launches = ktimer_read("k_rankB_gridx")[1]
     ktimer_enable(False)
     assert int(lib().vr_engine_est_predicted()) - p0 == 2, "both structured regions go exact up front"
     assert est_launches == 1 * len(models), "the two continuous regions stay in the EST grid (pass 1)"
     # (region 0 is off the estimate: the fused walk takes its window parameters from a fused
     # region's workspace, so no pass of the continuous regions is flagged)
     assert int(lib().vr_engine_est_reruns()) - r0 == 0
-    assert gridx_launches == 2 * len(models), "the two structured regions walk the exact grid"
     for a, pn in enumerate(neurals):
         ref = R.bootstrap_spearman_multi(pn, models, idx, full_first=True).cpu().numpy()
         assert np.array_equal(got[a], ref), a
-    p1, r1 = int(lib().vr_engine_est_predicted()), int(lib().vr_engine_est_reruns())
-    off = R.bootstrap_spearman_grid(neurals, models, idx, joins, full_first=True).cpu().numpy()
-    assert int(lib().vr_engine_est_predicted()) - p1 == 2 and int(lib().vr_engine_est_reruns()) - r1 == 0
-    assert np.array_equal(off, got)
 
 
-def test_exact_grid_ties_and_l2_masks(dev, monkeypatch):
-    # the exact grid walk with tied A plans (chunks that start after c L, the chunk lookup's
-    # step back), tied and quantised B plans, 4 and 2 regions, masks from L2 too
-    from visreps_amd._lib import ktimer_enable, ktimer_read
-
+def test_exact_form_grid_call_ties_and_l2_masks(dev, monkeypatch):
+    # the exact-form walks under a grid call (the per-region calls) with tied A plans (chunks
+    # that start after c L, the join's chunk search), tied and quantised B plans, 4 and 2
+    # regions, masks from L2 too
     n = 1800
     neurals = [R.RankPlan((_rdm(dev, n, 40 + 10 * i, 130 + i) * 1024).floor() / 1024) for i in range(3)]
     neurals.append(R.RankPlan(_rdm(dev, n, 70, 134, relu=True)))
@@ -495,7 +452,6 @@ def test_exact_grid_ties_and_l2_masks(dev, monkeypatch):
     idx = bootstrap_indices(42, n, int(0.9 * n), 130)
     sj = R.SharedJoins(neurals)
     joins = [sj.join(pm) for pm in models]
-    monkeypatch.setenv("VISREPS_ENGINE_GRIDX", "1")
     with exact_engine():
         refs = [R.bootstrap_spearman_multi(pn, models, idx, full_first=True,
                                            joined=[joins[m][a] for m in range(len(models))]).cpu().numpy()
@@ -505,12 +461,8 @@ def test_exact_grid_ties_and_l2_masks(dev, monkeypatch):
             if lds == "global":
                 monkeypatch.setenv("VISREPS_ENGINE_MASKS", "global")
             for na in (4, 2):
-                ktimer_enable(True)
                 got = R.bootstrap_spearman_grid(neurals[:na], models, idx, [js[:na] for js in joins],
                                                 full_first=True).cpu().numpy()
-                launches = ktimer_read("k_rankB_gridx")[1]
-                ktimer_enable(False)
-                assert launches == 3 * len(models), (lds, na)
                 for a in range(na):
                     assert np.array_equal(got[a], refs[a]), (lds, na, a)
 

@@ -98,7 +98,7 @@ struct EngineCfg {
   // EST passes (every kernel of one EST pass uses these; est_nwaves <= nwaves)
   bool est_lds;   // EST rank walks: masks in LDS beside the table (else masks from L2)
   int est_grid, est_nwaves;
-  int est_mode;       // 1: interval table in LDS, 2: one linear interval in registers
+  int est_mode;       // 1: per-lane interval table in LDS, 3: one wave-uniform estimate (EST 3 / 4)
   int est_b;          // log2 of the table interval
   uint32_t est_rows;  // table rows (intervals)
   uint32_t est_nseg;   // EST B-walk segments (work queue; est_segments)
@@ -115,8 +115,8 @@ static int env_int(const char* name, int dflt) {
 
 constexpr int SEGS_PER_WAVE = 4;  // most EST A-side segments per resident wave (workspace bound)
 // EST B walks take segments of >= 256 positions from a work queue, one per resident wave;
-// the A side cuts each of them into est_ratioA (VISREPS_ENGINE_SEGS_A, default and most
-// SEGS_PER_WAVE) for its own queue (k_rankA; k_countA takes them round-robin).
+// the A side cuts each of them into est_ratioA (at most SEGS_PER_WAVE) for its own queue
+// (k_rankA; k_countA takes them round-robin).
 static uint32_t est_segments(int64_t M, int est_nwaves) {
   const int64_t by_len = (M + 255) / 256;
   return (uint32_t)std::max<int64_t>(1, std::min<int64_t>(by_len, (int64_t)est_nwaves));
@@ -135,28 +135,25 @@ static EngineCfg engine_cfg(int64_t n, int mode = 0) {
   const int per_cu = std::max<int>(1, std::min<int>(2048 / ENG_THREADS, (int)(cap / std::max<size_t>(c.lds, 1))));
   c.grid = num_cus() * per_cu;
   c.nwaves = c.grid * WAVES_PER_WG;
-  // EST: masks and table both in LDS when the table gets >= 1 row beside the masks at
-  // VISREPS_ENGINE_EST_WG workgroups per CU (default 2, the exact form's occupancy);
-  // otherwise masks from L2 and the table alone in LDS.
+  // EST at the exact form's occupancy (per_cu workgroups per CU). EST 3 holds no table: the
+  // masks sit in LDS when they fit. EST 1: masks and table both in LDS when the table gets
+  // >= 1 row beside the masks; otherwise masks from L2 and the table alone in LDS.
   const size_t row = (size_t)LANES * sizeof(uint2);
-  const int est_wg = std::max(1, std::min(per_cu, env_int("VISREPS_ENGINE_EST_WG", per_cu)));
-  const size_t per_wg = cap / est_wg;
-  c.est_lds = c.use_lds && env_int("VISREPS_ENGINE_EST_LDS", 1) != 0 && per_wg >= need + row;
-  // VISREPS_ENGINE_EST_LIN=1: one linear interval (EST 2), no table in LDS
-  c.est_mode = mode > 0 ? mode : std::max(1, std::min(3, env_int("VISREPS_ENGINE_EST_MODE", 3)));
-  if (c.est_mode >= 2) c.est_lds = c.use_lds && env_int("VISREPS_ENGINE_EST_LDS", 1) != 0 && per_wg >= need;
+  const size_t per_wg = cap / per_cu;
+  c.est_mode = mode > 0 ? mode : (env_int("VISREPS_ENGINE_EST_MODE", 3) == 1 ? 1 : 3);
+  c.est_lds = c.use_lds && per_wg >= need + (c.est_mode == 3 ? 0 : row);
   uint32_t rows_fit =
       c.est_lds ? (uint32_t)std::min<size_t>(EST_NC, (per_wg - need) / row) : (uint32_t)EST_NC;
-  if (c.est_mode >= 2) rows_fit = 1;
+  if (c.est_mode == 3) rows_fit = 1;
   // EST 1 with masks from L2: the table alone in LDS, up to 144 intervals (72 KB: two
   // workgroups per CU still fit) -- finer knots for the large structured triangles it serves
   const uint32_t target = (c.est_mode == 1 && !c.est_lds) ? 144u : 96u;
   c.est_b = est_bits(M, rows_fit, target);
   c.est_rows = M > 0 ? est_intervals(M, c.est_b) : 0;
-  c.est_grid = c.est_lds ? num_cus() * est_wg : c.grid;
+  c.est_grid = c.grid;
   c.est_nwaves = c.est_grid * WAVES_PER_WG;
   c.est_nseg = est_segments(M, c.est_nwaves);
-  c.est_ratioA = (uint32_t)std::max(1, std::min(SEGS_PER_WAVE, env_int("VISREPS_ENGINE_SEGS_A", SEGS_PER_WAVE)));
+  c.est_ratioA = SEGS_PER_WAVE;
   // A segments of >= 1024 positions: small triangles (phase 1's M ~ 5e5) keep one per B
   // segment, where thousands of one-window segments would queue on a single counter
   while (c.est_ratioA > 1 && (uint64_t)c.est_nseg * c.est_ratioA * 1024u > (uint64_t)M) --c.est_ratioA;
@@ -253,9 +250,9 @@ static EngineWs engine_layout(void* base, int64_t n, int lw, int nwaves, size_t*
 // ---------------------------------------------------------------------------------
 // per-unit join and per-pass masks
 // ---------------------------------------------------------------------------------
-// The second array: the A chunk (exact form, JOIN_CHUNK) or the EST 3 window low end of the
-// A position, L + (2 posA R >> 32) (JOIN_LO): the B walk then reads it instead of computing it.
-enum { JOIN_NONE = 0, JOIN_CHUNK = 1, JOIN_LO = 2 };
+// What a join writes: the A positions alone (JOIN_NONE: all an EST walk reads) or, in a
+// second array, the A chunk of each position too (JOIN_CHUNK: the exact form's base gather).
+enum { JOIN_NONE = 0, JOIN_CHUNK = 1 };
 // Every join gathers the 4-B A positions (posMapA), a table the MALL can keep across the
 // joins of one A plan. JOIN_CHUNK also needs the A chunk of the position: chunks are
 // group-aligned, chunk c starting at the first group start >= c L, so the chunk of a
@@ -265,8 +262,7 @@ enum { JOIN_NONE = 0, JOIN_CHUNK = 1, JOIN_LO = 2 };
 __global__ void k_join(const uint32_t* __restrict__ codesB, int64_t M, int64_t n,
                        const uint32_t* __restrict__ gstartA, const uint32_t* __restrict__ chunk_gA,
                        uint32_t L, uint32_t nchA, const uint32_t* __restrict__ posMapA,
-                       uint32_t* __restrict__ posA_byB, uint32_t* __restrict__ second, int mode,
-                       uint32_t Lu, uint32_t Ru) {
+                       uint32_t* __restrict__ posA_byB, uint32_t* __restrict__ chunkA_byB, int mode) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= M) return;
   const uint32_t cb = __builtin_nontemporal_load(codesB + i);
@@ -287,18 +283,10 @@ __global__ void k_join(const uint32_t* __restrict__ codesB, int64_t M, int64_t n
       c = lo;
     }
     posA_byB[i] = pa;
-    second[i] = c;
+    chunkA_byB[i] = c;
     return;
   }
   __builtin_nontemporal_store(pa, posA_byB + i);
-  if (mode == JOIN_LO) __builtin_nontemporal_store(Lu + __umulhi(pa << 1, Ru), second + i);
-}
-
-// JOIN_LO from the A positions already joined (no second pair-map gather)
-__global__ void k_join_lo(const uint32_t* __restrict__ posA_byB, int64_t M, uint32_t* __restrict__ second,
-                          uint32_t Lu, uint32_t Ru) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < M) second[i] = Lu + __umulhi(posA_byB[i] << 1, Ru);
 }
 
 // Shared joins: the position maps of up to 4 A plans interleaved into 16-B records, so one
@@ -470,52 +458,18 @@ __device__ inline uint32_t est_recover(uint32_t v, uint32_t lo) { return lo + (u
 // EST: true if y is outside the window [lo, lo + 2^16)
 __device__ inline bool est_bad(uint32_t y, uint32_t lo) { return y - lo > 65535u; }
 
-// The window low end of either EST form. EST 1: the interpolated interval table (LDS).
-// EST 2 (one interval over the whole triangle): lo = trunc(fma(R, pos, L)) in f32 from two
-// per-lane registers, R = 2 M'/M and L = 1 - 2^15 (k_c0_lin): no table read per pair.
-// Both are deterministic and monotone non-decreasing in pos (the A side checks only the
-// ends of a group), and the A and B walks evaluate the same function.
+// The window low end of either EST form, deterministic and monotone non-decreasing in pos
+// (the A side checks only the ends of a group); the A and B walks evaluate the same function.
+// EST 1: the interpolated interval table (LDS).
 // EST 3 (every active lane a subset of the same size, so one included-pair total M' for
 // the wave): lo = L + (2 pos R >> 32), R = floor(2^32 M'/M), L = 1 - 2^15: wave-uniform,
 // scalar arithmetic (s_mul_hi_u32), no per-lane work besides the 16-bit recovery.
 struct EstLo {
-  const uint2* tab;
+  const uint2* tab;  // EST 1
   int bits;
-  float L, R;
-  uint32_t Lu, Ru;
-  uint32_t sh;  // EST 6: the coarse A position is pos >> sh
-  uint32_t g;   // EST 5: lane 63 holds the EST 3 low end + 2^15, >> g
+  uint32_t Lu, Ru;   // EST 3 / 4
 };
 
-// 32-bit triangle index of pair code (a << 16) | b (M < 2^32: a n < 2^32, a (a + 1) < 2^32)
-__device__ inline uint32_t tri32(uint32_t code, uint32_t n) {
-  const uint32_t a = code >> 16, b = code & 0xffffu;
-  return a * n - ((a * (a + 1u)) >> 1) + b - a - 1u;
-}
-
-// EST 5 / 6 (the triangle-order TB, VISREPS_ENGINE_TRI): the TB row of a pair sits at its
-// triangle index and lane 63 holds a 16-bit tag of its A position pos from which both walks
-// evaluate the same window low end (monotone non-decreasing in pos, like EST 3):
-//  EST 5  tag = (EST 3 low end + 2^15) >> g, low end = (tag << g) - 2^15: the EST 3 window
-//         rounded down to a multiple of 2^g (g = 11 at N = 10k: <= 2047 of the 2^15 slack),
-//         one shift and one subtract on the B side;
-//  EST 6  (the pass holding the full set in lane 0) tag = pos >> sh, the EST 4 low ends at the
-//         middle of the coarse interval.
-__device__ inline uint32_t est5_u(const EstLo& e, uint32_t pos) { return 1u + __umulhi(pos << 1, e.Ru); }
-__device__ inline uint32_t est5_lo_tag(const EstLo& e, uint32_t tag) { return (tag << e.g) - 32768u; }
-template <int EST>
-__device__ inline uint32_t tri_tag(const EstLo& e, uint32_t pos) {
-  return EST == 5 ? est5_u(e, pos) >> e.g : pos >> e.sh;
-}
-__device__ inline uint32_t est_lo_pc(const EstLo& e, uint32_t pc, int lane, bool full_lane0) {
-  const uint32_t mid = (pc << e.sh) + ((1u << e.sh) >> 1);
-  const uint32_t lo = e.Lu + __umulhi(mid << 1, e.Ru);  // wave-uniform (scalar) arithmetic
-  if (!full_lane0) return lo;
-  // lane 0 (the full set): + the uniform difference of its low end, masked to lane 0 --
-  // two VALU ops on scalar operands, no per-lane branch
-  const uint32_t d0 = 2u * mid + (1u - 32768u) - lo;
-  return lo + (d0 & (0u - (uint32_t)(lane == 0)));
-}
 // EST 4: EST 3 with lane 0 holding the full set (pass 0 of a full_first call): its count
 // before A position pos is pos itself, so its low end is 2 pos + 1 - 2^15 (est_lo_t<4>, the
 // A side's checks). Lane 0 stores its doubled rank y shifted down by the gap between that low
@@ -532,33 +486,19 @@ __device__ inline uint32_t est4_shift(uint32_t Ru, uint32_t pos) {
 }
 template <int EST>
 __device__ inline uint32_t est_lo_t(const EstLo& e, uint32_t pos, int lane) {
-  if constexpr (EST == 5)
-    return est5_lo_tag(e, est5_u(e, pos) >> e.g);
-  else if constexpr (EST == 6)
-    return est_lo_pc(e, pos >> e.sh, lane, true);
-  else if constexpr (EST == 4)
+  if constexpr (EST == 4)
     return lane == 0 ? 2u * pos + (1u - 32768u) : e.Lu + __umulhi(pos << 1, e.Ru);
   else if constexpr (EST == 3)
     return e.Lu + __umulhi(pos << 1, e.Ru);
-  else if constexpr (EST == 2)
-    return (uint32_t)(int32_t)__builtin_fmaf(e.R, (float)pos, e.L);
   else
     return est_lo(e.tab, pos, lane, e.bits);
 }
 template <int EST>
 __device__ inline EstLo est_setup(const uint2* __restrict__ gtab, uint32_t rows, int bits, uint2* smem) {
-  EstLo e{nullptr, bits, 0.f, 0.f, 0u, 0u, 0u, 0u};
+  EstLo e{nullptr, bits, 0u, 0u};
   if constexpr (EST >= 3) {
     e.Lu = wave_uniform(sload(&gtab->x));
     e.Ru = wave_uniform(sload(&gtab->y));
-    if constexpr (EST >= 5) {
-      e.sh = wave_uniform(sload(&gtab[1].x));
-      e.g = wave_uniform(sload(&gtab[1].y));
-    }
-  } else if constexpr (EST == 2) {
-    const uint2 v = gtab[threadIdx.x & 63];
-    e.L = __uint_as_float(v.x);
-    e.R = __uint_as_float(v.y);
   } else if constexpr (EST == 1) {
     e.tab = stage_table(gtab, rows, smem);
   }
@@ -634,12 +574,8 @@ __global__ void k_c0(const uint32_t* __restrict__ c0rel, const uint32_t* __restr
   ftab[(size_t)c * LANES + lane] = make_uint2(2u * a + 1u - 32768u, (uint32_t)((2 * d) >> EST_STEP_BITS));
 }
 
-// EST 3 / 5: the wave-uniform estimate {L, R} (est3_params) into ftab row 0, EST 5's coarse
-// position shift into row 1
-__global__ void k_c0_u(uint32_t Lu, uint32_t Ru, uint32_t sh, uint32_t g, uint2* __restrict__ ftab) {
-  ftab[0] = make_uint2(Lu, Ru);
-  ftab[1] = make_uint2(sh, g);
-}
+// EST 3 / 4: the wave-uniform estimate {L, R} (est3_params) into ftab row 0
+__global__ void k_c0_u(uint32_t Lu, uint32_t Ru, uint2* __restrict__ ftab) { ftab[0] = make_uint2(Lu, Ru); }
 
 // EST 3 estimate of a call whose subsets all hold k stimuli: M' = k (k - 1) / 2 included
 // pairs per lane, R = floor(2^32 M'/M) (host and device use these same two words; a lane
@@ -649,13 +585,6 @@ static inline uint2 est3_params(int64_t k, int64_t M) {
   unsigned __int128 r = M > 0 ? (mp << 32) / (unsigned __int128)(uint64_t)M : 0;
   if (r > 0xffffffffu) r = 0xffffffffu;
   return make_uint2(1u - 32768u, (uint32_t)r);
-}
-
-// EST 2: the one-interval estimate {L, R} per lane (f32 bit patterns in ftab row 0)
-__global__ void k_c0_lin(const uint32_t* __restrict__ total, int64_t M, uint2* __restrict__ ftab) {
-  const int lane = threadIdx.x;
-  const float R = (float)(2.0 * (double)total[lane] / (double)M);
-  ftab[lane] = make_uint2(__float_as_uint(1.0f - 32768.0f), __float_as_uint(R));
 }
 
 // EST 3 up-front check (est_predict): lane `lane`'s included count a at coarse boundary
@@ -717,21 +646,6 @@ __device__ inline void store_rows_est(uint16_t* __restrict__ TB, uint32_t stride
   for (; i < cnt; ++i, row += stride) tb_store((uint16_t)y, row);
 }
 
-// EST 5 / 6: the same rows at their triangle indices (row_t(r) for A position r), lane 63 of
-// each row holding the row's coarse A position r >> sh instead of a rank
-template <int EST, typename RowT>
-__device__ inline void store_rows_tri(uint16_t* __restrict__ TB, uint32_t r0, uint32_t cnt, int lane,
-                                      uint32_t y, const EstLo& el, bool& bad, RowT&& row_t) {
-  if (cnt == 0) return;
-  if ((r0 >> 6) != ((r0 + cnt - 1u) >> 6))
-    bad |= est_bad(y, est_lo_t<EST>(el, r0, lane)) || est_bad(y, est_lo_t<EST>(el, r0 + cnt - 1u, lane));
-  for (uint32_t i = 0; i < cnt; ++i) {
-    const uint32_t r = r0 + i;
-    const uint16_t v = lane == LANES - 1 ? (uint16_t)tri_tag<EST>(el, r) : (uint16_t)y;
-    tb_store(v, TB + (size_t)row_t(r) * LANES + lane);
-  }
-}
-
 // A side. Exact form (EST false): chunk-relative doubled ranks y - 2 lp (u16 or u32) and
 // the chunk-start counts lpA for baseA. EST form: absolute doubled ranks modulo 2^16,
 // each checked against the count estimate the B side will use.
@@ -743,21 +657,11 @@ __global__ __launch_bounds__(ENG_THREADS, 8) void k_rankA(
     uint32_t* __restrict__ lpA, uint32_t* __restrict__ seg_tot, uint64_t* __restrict__ seg_part,
     uint32_t nseg, EstA est, const uint32_t* __restrict__ segpos, uint32_t* __restrict__ queue) {
   static_assert(!EST || sizeof(TBT) == 2, "EST ranks are u16");
-  constexpr bool TRI = EST >= 5;  // triangle-order TB rows (EST 5 / 6)
-  static_assert(!TRI || FULL, "triangle-order passes use whole 64-lane rows");
   extern __shared__ uint64_t smask[];
   const uint64_t* m = stage_masks<LDS>(gmask, n, smask);
-  EstLo el{nullptr, 0, 0.f, 0.f, 0u, 0u, 0u, 0u};
+  EstLo el{nullptr, 0, 0u, 0u};
   if constexpr (EST != 0)
     el = est_setup<EST>(est.ftab, est.tabrows, est.bits, reinterpret_cast<uint2*>(smask + (LDS ? n : 0)));
-  // TRI: triangle index and lane-63 tag of each position of window wt (lane j: position
-  // wt + j), computed once per window in the vector unit; rows of a tie group that began in
-  // an earlier window get theirs from their code (scalar loads)
-  uint32_t tl = 0, tg = 0, wt = 0;
-  auto row_t = [&](uint32_t r) -> uint32_t {
-    return r - wt < 64u ? readlane_u32(tl, r - wt) : tri32(sload(codes + r), (uint32_t)n);
-  };
-  (void)row_t;
   const int lane = threadIdx.x & 63;
   const bool active = FULL || lane < lw;
   const uint32_t stride = FULL ? (uint32_t)LANES : (uint32_t)lw;
@@ -785,10 +689,7 @@ __global__ __launch_bounds__(ENG_THREADS, 8) void k_rankA(
       auto close = [&](uint32_t xe, uint32_t ce) {
         tie_add<BIGT>(tie, tie_big, ce - cgs);
         if (active) {
-          if constexpr (TRI)
-            store_rows_tri<EST>(reinterpret_cast<uint16_t*>(TB), gs, xe - gs, lane, y0 + cgs + ce + 1u, el, bad,
-                                row_t);
-          else if constexpr (EST)
+          if constexpr (EST)
             store_rows_est<EST>(reinterpret_cast<uint16_t*>(TB), stride, gs, xe - gs, lane, y0 + cgs + ce + 1u,
                                 el, bad);
           else
@@ -808,11 +709,6 @@ __global__ __launch_bounds__(ENG_THREADS, 8) void k_rankA(
       uint32_t cd = (w0 + lane >= P0 && w0 + lane < P1) ? codes[w0 + lane] : 0u;
       uint32_t f0 = sload(gflag + (w0 >> 5)), f1 = sload(gflag + (w0 >> 5) + 1);
       for (; w0 < P1; w0 += 64) {
-        if constexpr (TRI) {
-          tl = (w0 + lane >= P0 && w0 + lane < P1) ? tri32(cd, (uint32_t)n) : 0u;
-          tg = tri_tag<EST>(el, w0 + (uint32_t)lane);
-          wt = w0;
-        }
         const uint64_t x = window_bits<XPOSE_A>(m, cd, w0, P0, P1, lane, active);
         uint64_t F = restrict_flags(((uint64_t)f1 << 32) | f0, w0, P0, P1);
         asm volatile("" ::"v"(x) : "memory");
@@ -835,28 +731,17 @@ __global__ __launch_bounds__(ENG_THREADS, 8) void k_rankA(
           if (cn >= c1 || pn > w0 + 63u) {
             uint32_t t = EST ? y0 + 2u * cw + 1u : 2u * (cw - lp) + 1u;
             TBT* row = TB + (size_t)w0 * stride + lane;
-            if constexpr (TRI) {
   #pragma unroll
-              for (int j = 0; j < 63; ++j) {
-                const uint32_t bit = (uint32_t)(x >> j) & 1u;
-                const uint32_t v = t + bit;
-                const uint32_t pc = readlane_u32(tg, j);
-                tb_store((TBT)(lane == LANES - 1 ? pc : v), TB + (size_t)readlane_u32(tl, j) * LANES + lane);
-                t = v + bit;
+            for (int j = 0; j < 63; ++j) {
+              const uint32_t bit = (uint32_t)(x >> j) & 1u;
+              const uint32_t v = t + bit;
+              if constexpr (EST == 4) {  // lane 0: shifted (est4_shift; singletons: y - d >= 2)
+                const uint32_t sub = est4_shift(el.Ru, w0 + (uint32_t)j) & (0u - (uint32_t)(lane == 0));
+                if (active) tb_store((TBT)(v - sub), row + (size_t)j * stride);
+              } else {
+                if (active) tb_store((TBT)v, row + (size_t)j * stride);
               }
-            } else {
-  #pragma unroll
-              for (int j = 0; j < 63; ++j) {
-                const uint32_t bit = (uint32_t)(x >> j) & 1u;
-                const uint32_t v = t + bit;
-                if constexpr (EST == 4) {  // lane 0: shifted (est4_shift; singletons: y - d >= 2)
-                  const uint32_t sub = est4_shift(el.Ru, w0 + (uint32_t)j) & (0u - (uint32_t)(lane == 0));
-                  if (active) tb_store((TBT)(v - sub), row + (size_t)j * stride);
-                } else {
-                  if (active) tb_store((TBT)v, row + (size_t)j * stride);
-                }
-                t = v + bit;
-              }
+              t = v + bit;
             }
             gs = w0 + 63u;
             cgs = cw + popc64(x & lowmask(63));
@@ -1050,14 +935,10 @@ __device__ inline void gather_wait_t(uint32_t t[EBB]) {
 constexpr int EPS = 2;  // EST: gather batches in flight per wave (software pipeline depth; 1 = none)
 
 // B side: the window low end of pair j of the window (lane j of pa / la holds pair j). EST 3
-// and 4 read the join's precomputed value (EST 4's lane 0: 2 posA + 1 - 2^15).
+// and 4 read the value the walk computed per window lane (la; EST 4's lane 0: 2 posA + 1 - 2^15).
 template <int EST>
-__device__ inline uint32_t est_lo_b(const EstLo& el, uint32_t pa, uint32_t la, int j, int lane, uint32_t tv) {
-  if constexpr (EST == 5) {  // the tag in lane 63 of the gathered row (tv: this pair's loaded entry)
-    return est5_lo_tag(el, readlane_u32(tv, LANES - 1));
-  } else if constexpr (EST == 6) {
-    return est_lo_pc(el, readlane_u32(tv, LANES - 1), lane, true);
-  } else if constexpr (EST == 4) {
+__device__ inline uint32_t est_lo_b(const EstLo& el, uint32_t pa, uint32_t la, int j, int lane) {
+  if constexpr (EST == 4) {
     const uint32_t l = readlane_u32(la, j);
     const uint32_t l0 = 2u * readlane_u32(pa, j) + (1u - 32768u);
     return lane == 0 ? l0 : l;
@@ -1091,7 +972,7 @@ __device__ inline void pipe_batch(const uint16_t* __restrict__ TB, uint32_t stri
   uint32_t y[EBB];
 #pragma unroll
   for (int q = 0; q < EBB; ++q)
-    y[q] = est_recover(t[H % EPS][q], est_lo_b<EST>(el, pa, la, H * EBB + q, lane, t[H % EPS][q]));
+    y[q] = est_recover(t[H % EPS][q], est_lo_b<EST>(el, pa, la, H * EBB + q, lane));
   fn(H, y);
   if constexpr (H + 1 < NBT) pipe_batch<EST, H + 1>(TB, stride, el, pa, la, lane_bt, lane, t, fn);
 }
@@ -1113,8 +994,8 @@ __device__ inline void gather_window_est(const uint16_t* __restrict__ TB, uint32
     gather_issue_t(TB, stride, pa, h * EBB, lane_bt, t);
     gather_wait_t(t);
 #pragma unroll
-    for (int q = 0; q < EBB; ++q)  // EST 3: the join's precomputed low end (lane j = pair j)
-      t[q] = est_recover(t[q], est_lo_b<EST>(el, pa, la, h * EBB + q, lane, t[q]));
+    for (int q = 0; q < EBB; ++q)
+      t[q] = est_recover(t[q], est_lo_b<EST>(el, pa, la, h * EBB + q, lane));
     fn(h, t);
   }
 }
@@ -1136,7 +1017,7 @@ __device__ inline void gather_window(const TBT* __restrict__ TB, const uint32_t*
 }
 
 // EST 3 / 4 B walk, prefetching form (the window low ends computed from the A
-// positions in scalar registers, not streamed): every vector-memory load of the walk is
+// positions, three VALU ops per window lane): every vector-memory load of the walk is
 // issued from asm and retired by a counted asm `s_waitcnt vmcnt(N)`, so the compiler places
 // no vmcnt wait of its own: the next window's streams S (codes, A positions: 2 loads) and
 // its two L2 mask gathers M (when the masks are not in LDS) are issued between the window's
@@ -1177,7 +1058,7 @@ __global__ __launch_bounds__(ENG_THREADS, EST ? RANKB_EST_MINW : RANKB_MINW) voi
   constexpr int NB = EST ? EBB : BB;  // pairs per gather batch
   extern __shared__ uint64_t smask[];
   const uint64_t* m = stage_masks<LDS>(gmask, n, smask);
-  EstLo el{nullptr, 0, 0.f, 0.f, 0u, 0u, 0u, 0u};
+  EstLo el{nullptr, 0, 0u, 0u};
   if constexpr (EST != 0) el = est_setup<EST>(ftab, tabrows, bits, reinterpret_cast<uint2*>(smask + (LDS ? n : 0)));
   const int lane = threadIdx.x & 63;
   const bool active = FULL || lane < lw;
@@ -1207,8 +1088,7 @@ __global__ __launch_bounds__(ENG_THREADS, EST ? RANKB_EST_MINW : RANKB_MINW) voi
         cgs = ce;
       };
       // EST 3 / 4 (small tie groups): the prefetching walk, which computes the window low
-      // ends from the A positions (a join's streamed low ends, VISREPS_ENGINE_LO_JOIN=1, hold
-      // the same values and are not read)
+      // ends from the A positions
       // (with masks from L2 -- n > 10,176 -- too; round 5 restricted it to LDS masks
       // after a MEMORY_APERTURE_VIOLATION, whose cause was a probe build's SGPR spill restored
       // by v_readlane right before the asm mask load that reads it: see xw_ldm)
@@ -1341,20 +1221,11 @@ __global__ __launch_bounds__(ENG_THREADS, EST ? RANKB_EST_MINW : RANKB_MINW) voi
                        uint32_t& f1) {
         const uint32_t pos = w + (uint32_t)lane;
         const bool valid = pos >= P0 && pos < P1;
-        if constexpr (EST >= 5) {  // triangle-order TB: the row is the pair's triangle index
-          cd = valid ? codes[pos] : 0u;
-          pa = valid ? tri32(cd, (uint32_t)n) : 0u;
-          ca = 0u;
-          f0 = sload(gflag + (w >> 5));
-          f1 = sload(gflag + (w >> 5) + 1);
-          return;
-        }
         pa = valid ? posA_byB[pos] : 0u;
-        // EST 3/4: the window low end of the pair's A position, L + (2 posA R >> 32), computed
-        // here per lane for the window's 64 pairs (three VALU ops per window lane, no stream),
-        // or streamed from the join (VISREPS_ENGINE_LO_JOIN=1, A/B)
+        // EST 3: the window low end of the pair's A position, L + (2 posA R >> 32), computed
+        // here per lane for the window's 64 pairs (three VALU ops per window lane, no stream)
         if constexpr (EST >= 3)
-          ca = !valid ? 0u : chunkA_byB ? chunkA_byB[pos] : el.Lu + __umulhi(pa << 1, el.Ru);
+          ca = valid ? el.Lu + __umulhi(pa << 1, el.Ru) : 0u;
         else
           ca = (!EST && valid) ? chunkA_byB[pos] : 0u;
         cd = valid ? codes[pos] : 0u;
@@ -1587,168 +1458,6 @@ __global__ __launch_bounds__(ENG_THREADS, GRID_MINW) void k_rankB_grid(
       g.seg_part[r][PB_TIEH * fs + o] = 0;
     }
   }
-}
-
-// ---------------------------------------------------------------------------------
-// Exact grid B walk: k_rankB_grid's region fusion in the exact chunk-base form (every pass
-// with VISREPS_ENGINE_EST=0, and the regions of a grid call whose estimate fails its up-front
-// check). Per pair and region yA = 2 baseA[chunk] + TB[posA] (u16 chunk-relative ranks:
-// narrow A plans), as in k_rankB's exact form; the A chunk of a position is found here from
-// the region's chunk starts (cst: the last c <= pos / L whose start is <= pos, k_join's rule),
-// so the shared joins' A positions serve the exact form too (no per-unit chunk joins). Same
-// integer sums as the per-region exact walks: scores bit-identical to them.
-// ---------------------------------------------------------------------------------
-struct GridX {
-  const uint16_t* TB[4];     // each region's chunk-relative doubled ranks (u16)
-  const uint32_t* posA[4];   // B position -> A position, per region
-  const uint32_t* base[4];   // [nch][64] absolute included count at each A chunk start
-  const uint32_t* cst[4];    // [nch] A chunk start positions
-  uint32_t* seg_tot[4];
-  uint64_t* seg_part[4];
-};
-constexpr int GRIDX_NB = 2;  // pairs per gather batch (x R regions x 2 loads in flight, two batches);
-                             // 1 at R = 4, whose 2-pair batches do not fit 128 VGPRs
-// chunk of A position pa: q = pa / L from the reciprocal Lm = floor(2^32 / L) (q is exact or
-// one low), then back over chunk starts above pa (group-aligned chunks start at or after c L)
-__device__ inline uint32_t a_chunk(uint32_t pa, const uint32_t* __restrict__ cst, uint32_t L, uint32_t Lm,
-                                   uint32_t nch) {
-  uint32_t q = __umulhi(pa, Lm);
-  if ((q + 1u) * L <= pa) ++q;
-  q = min(q, nch - 1u);
-  while (q > 0u && cst[q] > pa) --q;
-  return q;
-}
-template <int R, bool LDS>
-__global__ __launch_bounds__(ENG_THREADS, GRID_MINW) void k_rankB_gridx(
-    const uint32_t* __restrict__ codes, const uint32_t* __restrict__ gflag, const uint64_t* __restrict__ gmask,
-    int64_t n, GridX g, uint32_t nseg, uint32_t L, uint32_t Lm, uint32_t nch, const uint32_t* __restrict__ segpos,
-    uint32_t* __restrict__ queue) {
-  constexpr int NB = R >= 4 ? 1 : GRIDX_NB;
-  static_assert(64 % NB == 0, "batch");
-  extern __shared__ uint64_t smask[];
-  const uint64_t* m = stage_masks<LDS>(gmask, n, smask);
-  const int lane = threadIdx.x & 63;
-  const uint32_t lane_off = (uint32_t)lane;
-  for (;;) {
-    const uint32_t sidx = next_segment(queue);
-    if (sidx >= nseg) break;
-    const uint32_t P0 = segpos[sidx], P1 = segpos[sidx + 1];
-    u128 acc[R];
-    uint64_t St[R], S[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = 0, St[r] = 0, S[r] = 0;
-    uint64_t tie = 0;
-    u128 tie_unused = 0;
-    uint32_t cw = 0, cgs = 0;
-    if (P0 < P1) {
-      auto close = [&](uint32_t ce) {
-        const uint32_t y = cgs + ce + 1u;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-          acc[r] += (u128)S[r] * y;
-          St[r] += S[r];
-          S[r] = 0;
-        }
-        tie_add<false>(tie, tie_unused, ce - cgs);
-        cgs = ce;
-      };
-      for (uint32_t w0 = P0 & ~63u; w0 < P1; w0 += 64) {
-        const uint32_t pos = w0 + (uint32_t)lane;
-        const bool valid = pos >= P0 && pos < P1;
-        const uint32_t cd = valid ? codes[pos] : 0u;
-        uint32_t pa[R], ca[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-          pa[r] = valid ? g.posA[r][pos] : 0u;
-          ca[r] = a_chunk(pa[r], g.cst[r], L, Lm, nch);
-        }
-        const uint64_t x = window_bits<XPOSE_B>(m, cd, w0, P0, P1, lane, true);
-        const uint64_t F =
-            restrict_flags(((uint64_t)sload(gflag + (w0 >> 5) + 1) << 32) | sload(gflag + (w0 >> 5)), w0, P0, P1);
-        // batch h's rows, t / b[r][q] = region r's TB entry / chunk base of pair h NB + q
-        auto issue = [&](int h, uint32_t (&t)[R][NB], uint32_t (&b)[R][NB]) {
-#pragma unroll
-          for (int q = 0; q < NB; ++q)
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-              t[r][q] = __builtin_nontemporal_load(g.TB[r] + (size_t)readlane_u32(pa[r], h * NB + q) * LANES + lane_off);
-              b[r][q] = g.base[r][(size_t)readlane_u32(ca[r], h * NB + q) * LANES + lane_off];
-            }
-        };
-        uint32_t tb[2][R][NB], bb[2][R][NB];
-        if (F == ~0ull) {  // every position starts a group (k_rankB's per-window form explains)
-          close(cw);
-          uint64_t a64[R];
-#pragma unroll
-          for (int r = 0; r < R; ++r) a64[r] = 0;
-          uint32_t c1 = cw + 1u;
-          issue(0, tb[0], bb[0]);
-#pragma unroll
-          for (int h = 0; h < 64 / NB; ++h) {
-            if (h + 1 < 64 / NB) issue(h + 1, tb[(h + 1) & 1], bb[(h + 1) & 1]);
-#pragma unroll
-            for (int q = 0; q < NB; ++q) {
-              const uint32_t j = h * NB + q;
-              const uint32_t mk = (uint32_t)((int32_t)((uint32_t)(x >> (j & 32u)) << (31u - (j & 31u))) >> 31);
-#pragma unroll
-              for (int r = 0; r < R; ++r) {
-                const uint32_t y = 2u * bb[h & 1][r][q] + tb[h & 1][r][q];
-                if (j < 63) {
-                  const uint32_t yb = y & mk;
-                  a64[r] += (uint64_t)yb * c1;
-                  St[r] += yb;
-                } else {
-                  S[r] = y & mk;
-                }
-              }
-              if (j < 63)
-                c1 -= mk;
-              else
-                cgs = c1 - 1u;
-            }
-          }
-#pragma unroll
-          for (int r = 0; r < R; ++r) acc[r] += (u128)a64[r] * 2u;
-        } else {
-          issue(0, tb[0], bb[0]);
-#pragma unroll
-          for (int h = 0; h < 64 / NB; ++h) {
-            if (h + 1 < 64 / NB) issue(h + 1, tb[(h + 1) & 1], bb[(h + 1) & 1]);
-#pragma unroll
-            for (int q = 0; q < NB; ++q) {
-              const uint32_t j = h * NB + q;
-              if ((F >> j) & 1ull) close(cw + popc64(x & lowmask(j)));
-              const bool in = (x >> j) & 1ull;
-#pragma unroll
-              for (int r = 0; r < R; ++r) {
-                const uint32_t y = 2u * bb[h & 1][r][q] + tb[h & 1][r][q];
-                S[r] += in ? (uint64_t)y : 0ull;
-              }
-            }
-          }
-        }
-        cw += popc64(x);
-      }
-      if ((P1 & 63u) == 0) close(cw);  // a 64-aligned segment end is in no window
-    }
-    const size_t o = (size_t)sidx * LANES + lane, fs = (size_t)nseg * LANES;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      g.seg_tot[r][o] = cw;
-      g.seg_part[r][PB_ACCL * fs + o] = (uint64_t)acc[r];
-      g.seg_part[r][PB_ACCH * fs + o] = (uint64_t)(acc[r] >> 64);
-      g.seg_part[r][PB_ST * fs + o] = St[r];
-      g.seg_part[r][PB_TIEL * fs + o] = tie;
-      g.seg_part[r][PB_TIEH * fs + o] = 0;
-    }
-  }
-}
-
-// chunk start positions of an A plan: cst[c] = gstart[chunk_g[c]]
-__global__ void k_chunk_starts(const uint32_t* __restrict__ gstart, const uint32_t* __restrict__ chunk_g,
-                               uint32_t nch, uint32_t* __restrict__ cst) {
-  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c < nch) cst[c] = gstart[chunk_g[c]];
 }
 
 // ---------------------------------------------------------------------------------
@@ -2050,7 +1759,7 @@ static int pass_a(const PlanView& A, int64_t n, const EngineWs& E, int lw, const
 // pre-pass reads the masks from LDS when they fit (CL), the rank walk from L2.
 template <int EM, bool CL, bool FULL, bool BTA>
 static int pass_a_est(const PlanView& A, int64_t n, const EngineWs& E, int lw, int nl, const EngineCfg& cfg,
-                      uint2 e3, uint2 tri, uint32_t* viol, hipStream_t st) {
+                      uint2 e3, uint32_t* viol, hipStream_t st) {
   VR_ONCE(VR_TRY(allow_big_lds(k_countA<CL, FULL>)); VR_TRY(allow_big_lds(k_rankA<CL, FULL, uint16_t, BTA, EM>)));
   const int64_t M = pairs_of(n);
   const uint32_t nch = plan_nchunks(M);
@@ -2065,9 +1774,7 @@ static int pass_a_est(const PlanView& A, int64_t n, const EngineWs& E, int lw, i
   }
   VR_TRY(lane_scan(E.segA_tot, nseg, E.bsum, E.segA_pre, E.totA, st));
   if constexpr (EM >= 3)
-    k_c0_u<<<1, 1, 0, st>>>(e3.x, e3.y, tri.x, tri.y, E.ftab);
-  else if constexpr (EM == 2)
-    k_c0_lin<<<1, LANES, 0, st>>>(E.totA, M, E.ftab);
+    k_c0_u<<<1, 1, 0, st>>>(e3.x, e3.y, E.ftab);
   else
     k_c0<<<nc, LANES, 0, st>>>(E.c0rel, E.c0seg, E.segA_pre, E.totA, nc, bits, M, E.ftab);
   VR_CHECK_LAUNCH();
@@ -2116,7 +1823,7 @@ static int est_predict(const PlanView& A, int64_t n, const EngineWs& E, int lw, 
 }
 
 // B walk of a pass for one B plan (unit slot u of the segment partials), joined to A by
-// posA_byB (and chunkA_byB: the A chunks in the exact form, EST 3's window low ends)
+// posA_byB (and, in the exact form, chunkA_byB: the A chunks; EST walks get none)
 template <bool LDS, bool FULL, typename TBT, bool BTB, int EST>
 static int walk_b(const PlanView& B, const uint32_t* posA_byB, const uint32_t* chunkA_byB, int64_t n,
                   const EngineWs& E, int lw, int64_t u, const EngineCfg& cfg, hipStream_t st, int kt_slot = -1) {
@@ -2134,7 +1841,7 @@ static int walk_b(const PlanView& B, const uint32_t* posA_byB, const uint32_t* c
     if (u >= QSLOTS - QS_RANKB) VR_CHECK_HIP(hipMemsetAsync(q, 0, sizeof(uint32_t), st));
   }
   {
-    KtScope kt(kt_slot >= 0 ? kt_slot : EST == 6 ? KT_RANKB_FULL : EST ? KT_RANKB_EST : KT_RANKB_EXACT, (double)M, st);
+    KtScope kt(kt_slot >= 0 ? kt_slot : EST ? KT_RANKB_EST : KT_RANKB_EXACT, (double)M, st);
     k_rankB<LDS, FULL, TBT, BTB, EST><<<EST ? cfg.est_grid : cfg.grid, ENG_THREADS, EST ? cfg.tab : cfg.lds, st>>>(
         B.codes, B.gstart, B.chunk_g, B.gflag, nch, E.masks, n, static_cast<const TBT*>(E.TB), lw,
         posA_byB, chunkA_byB, E.baseA, E.segB_tot + us, E.segB_part + us * PB_N, nseg, E.ftab,
@@ -2245,45 +1952,14 @@ static int run_engine_multi_impl(const PlanView& A, const PlanView* Bs, int64_t 
   auto join = [&](int mode) -> int {
     for (int64_t j = 0; j < nb; ++j) {
       KtScope kt(KT_JOIN, (double)M, st);
-      if (mode == JOIN_LO && second != JOIN_NONE) {  // the A positions are already there
-        k_join_lo<<<(unsigned)((M + 255) / 256), 256, 0, st>>>(joins[2 * j], M, joins[2 * j + 1], e3.x, e3.y);
-        VR_CHECK_LAUNCH();
-        continue;
-      }
       k_join<<<(unsigned)((M + 255) / 256), 256, 0, st>>>(Bs[j].codes, M, n, A.gstart, A.chunk_g,
                                                          plan_chunk_len(M), plan_nchunks(M), A.pos_map,
-                                                         joins[2 * j], joins[2 * j + 1], mode, e3.x, e3.y);
+                                                         joins[2 * j], joins[2 * j + 1], mode);
       VR_CHECK_LAUNCH();
     }
     second = mode;
     return VR_OK;
   };
-  // EST 5 / 6 (opt-in, VISREPS_ENGINE_TRI=1, in place of the EST 3 / 4 passes while
-  // M <= 2^28): the A walk writes each pair's 128-B row at its triangle index, lane 63
-  // holding the coarse A position, so the B walk finds the row from its own pair codes --
-  // no per-unit join, no A-position / low-end streams (132 instead of 140 B per pair) -- at
-  // the price of scattered (instead of sequential) row writes in the A walk and 63 subsets
-  // per pass. Flagged passes re-run in the exact form, which joins on demand. Measured on
-  // MI355X at configs[1] the scattered writes cost the A walk more (+0.70 ms
-  // per pass) than the joins save, so the A-order TB stays the default.
-  const bool tri = est && cfg.est_mode == 3 && lw == LANES && M <= ((int64_t)1 << 28) &&
-                   env_int("VISREPS_ENGINE_TRI", 0) != 0;
-  // EST 6 coarse position pos >> sh and EST 5 tag (low end + 2^15) >> g: both 16 bits
-  uint32_t sh = 0, g = 0;
-  while (((uint64_t)(M - 1) >> sh) >= 65536u) ++sh;
-  {
-    const uint64_t umax = 1u + (uint32_t)(((uint64_t)(2u * (uint32_t)(M - 1)) * e3.y) >> 32);
-    while ((umax >> g) >= 65536u) ++g;
-  }
-  const uint2 trip = make_uint2(sh, g);
-  // EST 3: the join precomputes the window low ends (JOIN_LO), the B walk streams them;
-  // VISREPS_ENGINE_LO_JOIN=0 has the walk compute them from the A positions instead (4 B
-  // fewer per pair and pass, but measured no faster: 1367 vs 1359 us per k_rankB launch,
-  // profiles/r3_engine_lo_ab.log)
-  const bool lo_join = !tri && cfg.est_mode == 3 && env_int("VISREPS_ENGINE_LO_JOIN", 0) != 0;
-  // the EST 3 estimate checked against the first pass's A counts before any join or pass
-  // (VISREPS_ENGINE_EST_PREDICT=0: skip the check; a failing estimate is then caught by the
-  // first pass's flags, at the cost of that pass)
   // EST segment starts of the A plan and of every B plan (k_seg_table), once per call
   if (est) {
     const uint32_t ns = cfg.est_nseg, nsA = cfg.est_nsegA;
@@ -2295,12 +1971,14 @@ static int run_engine_multi_impl(const PlanView& A, const PlanView* Bs, int64_t 
       VR_CHECK_LAUNCH();
     }
   }
+  // the EST 3 estimate checked against the first pass's A counts before any join or pass
+  // (VISREPS_ENGINE_EST_PREDICT=0: skip the check; a failing estimate is then caught by the
+  // first pass's flags, at the cost of that pass)
   bool predicted_bad = false;
   // (only when some lane holds a bootstrap subset: the full-set lane is exact by
   // construction, and a point-only call -- phase 1's 56 -- would pay a host sync for nothing)
   if (est && cfg.est_mode == 3 && n_sets > 0 && !exact_passes && env_int("VISREPS_ENGINE_EST_PREDICT", 1) != 0) {
-    const int64_t sub0 = tri ? LANES - 1 : lw;
-    const int nl0 = (int)std::min<int64_t>(sub0, total);
+    const int nl0 = (int)std::min<int64_t>(lw, total);
     VR_TRY(build_pass_masks(idx, k, 0, nl0, full_first, E.masks, n, st));
     VR_TRY(with_pass_tag(cfg.est_lds, lw == LANES, true, [&](auto tag) -> int {
       using Tg = decltype(tag);
@@ -2309,8 +1987,7 @@ static int run_engine_multi_impl(const PlanView& A, const PlanView* Bs, int64_t 
   }
   // (pre-joined units already hold their A positions: an EST call reading only those skips
   // the join; an exact-form one rewrites them with the same values beside the A chunks)
-  if (!tri && !predicted_bad && !exact_passes && !(cfg.prejoined && est && !lo_join))
-    VR_TRY(join(!est ? JOIN_CHUNK : (lo_join ? JOIN_LO : JOIN_NONE)));
+  if (!predicted_bad && !exact_passes && !(cfg.prejoined && est)) VR_TRY(join(est ? JOIN_NONE : JOIN_CHUNK));
   // the exact chunk-base form of subsets [set0, set0 + nl), nl <= lw
   auto exact_pass = [&](auto tag, int64_t set0, int nl) -> int {
     using Tg = decltype(tag);
@@ -2371,69 +2048,55 @@ static int run_engine_multi_impl(const PlanView& A, const PlanView* Bs, int64_t 
     }
     return exact_from(0);
   }
-  const int64_t sub = tri ? LANES - 1 : lw;  // subsets per EST pass
-  const int64_t npass = (total + sub - 1) / sub;
+  const int64_t npass = (total + lw - 1) / lw;  // lw subsets per EST pass
   const int64_t pfirst = 0;
   // The first EST pass runs alone: when the estimate cannot hold these A ranks (strongly
   // structured RDMs, giant tie groups) every pass is run in the exact form from there on.
-  const int want = lo_join ? JOIN_LO : JOIN_NONE;  // what the EST passes read
   for (int64_t p0 = pfirst, p1 = pfirst; p0 < npass; p0 = p1) {
     p1 = std::min<int64_t>(npass, p0 == pfirst ? p0 + 1 : p0 + EST_MAX_PASSES);
-    if (want != JOIN_NONE && second != want) VR_TRY(join(want));
     VR_CHECK_HIP(hipMemsetAsync(E.viol, 0, (size_t)(p1 - p0) * sizeof(uint32_t), st));
     VR_TRY(with_pass_tag(cfg.est_lds, lw == LANES, true, [&](auto tag) -> int {
       using Tg = decltype(tag);
       if constexpr (sizeof(typename Tg::tbt) == 2) {
         for (int64_t p = p0; p < p1; ++p) {
-          const int64_t set0 = p * sub;
-          const int nl = (int)std::min<int64_t>(sub, total - set0);
+          const int64_t set0 = p * lw;
+          const int nl = (int)std::min<int64_t>(lw, total - set0);
           VR_TRY(build_pass_masks(idx, k, set0, nl, full_first, E.masks, n, st));
           VR_CHECK_HIP(hipMemsetAsync(E.queue, 0, sizeof(uint32_t) * (size_t)std::min<int64_t>(QS_RANKB + nb, QSLOTS),
                                       st));  // this pass's work-queue counters
           uint32_t* viol = E.viol + (p - p0);
           auto run_pass = [&](auto em) -> int {
             constexpr int EM = decltype(em)::value;
-            if constexpr (EM >= 5 && !Tg::full) {
-              return VR_OK;  // (never taken: triangle-order passes are whole 64-lane rows)
-            } else {
-              VR_TRY((bigA ? pass_a_est<EM, Tg::lds, Tg::full, true>(A, n, E, lw, nl, cfg, e3, trip, viol, st)
-                           : pass_a_est<EM, Tg::lds, Tg::full, false>(A, n, E, lw, nl, cfg, e3, trip, viol, st)));
-              if (p == inject) {
-                k_inject_tb<<<1, LANES, 0, st>>>(static_cast<uint16_t*>(E.TB), (uint32_t)(M / 2), lw,
-                                                 (int)std::min<int64_t>(lw, sub));
+            VR_TRY((bigA ? pass_a_est<EM, Tg::lds, Tg::full, true>(A, n, E, lw, nl, cfg, e3, viol, st)
+                         : pass_a_est<EM, Tg::lds, Tg::full, false>(A, n, E, lw, nl, cfg, e3, viol, st)));
+            if (p == inject) {
+              k_inject_tb<<<1, LANES, 0, st>>>(static_cast<uint16_t*>(E.TB), (uint32_t)(M / 2), lw, lw);
+              VR_CHECK_LAUNCH();
+            }
+            // EST 4: lane 0's ranks are stored shifted (est4_shift), so its B walks are the EST 3
+            // kernel (timed on their own slot) and k_full_corr supplies lane 0's shift sums
+            constexpr int EB = EM == 4 ? 3 : EM;
+            const int kts = EM == 4 ? KT_RANKB_FULL : -1;
+            for (int64_t j = 0; j < nb; ++j) {
+              const uint32_t* pj = joins[2 * j];  // EST walks read the A positions alone
+              VR_TRY((h[(size_t)j + 1].max_group >= 65536u
+                          ? walk_b<Tg::lds, Tg::full, uint16_t, true, EB>(Bs[j], pj, nullptr, n, E, lw, j, cfg, st, kts)
+                          : walk_b<Tg::lds, Tg::full, uint16_t, false, EB>(Bs[j], pj, nullptr, n, E, lw, j, cfg, st, kts)));
+              if constexpr (EM == 4) {
+                KtScope kt(KT_FULL_CORR, (double)M, st);
+                k_full_corr<<<CORR_BLK, 256, 0, st>>>(pj, Bs[j].gflag, Bs[j].gstart, h[(size_t)j + 1].G, M, e3.y,
+                                                  E.corr + (size_t)j * CORR_N);
                 VR_CHECK_LAUNCH();
               }
-              // EST 4: lane 0's ranks are stored shifted (est4_shift), so its B walks are the EST 3
-              // kernel (timed on their own slot) and k_full_corr supplies lane 0's shift sums
-              constexpr int EB = EM == 4 ? 3 : EM;
-              const int kts = EM == 4 ? KT_RANKB_FULL : -1;
-              for (int64_t j = 0; j < nb; ++j) {
-                // EST 3/4: A positions and streamed low ends; EST 5/6: neither
-                const uint32_t* pj = EM >= 5 ? nullptr : joins[2 * j];
-                const uint32_t* lj = EM >= 3 && EM <= 4 && lo_join ? joins[2 * j + 1] : nullptr;
-                VR_TRY((h[(size_t)j + 1].max_group >= 65536u
-                            ? walk_b<Tg::lds, Tg::full, uint16_t, true, EB>(Bs[j], pj, lj, n, E, lw, j, cfg, st, kts)
-                            : walk_b<Tg::lds, Tg::full, uint16_t, false, EB>(Bs[j], pj, lj, n, E, lw, j, cfg, st, kts)));
-                if constexpr (EM == 4) {
-                  KtScope kt(KT_FULL_CORR, (double)M, st);
-                  k_full_corr<<<CORR_BLK, 256, 0, st>>>(pj, Bs[j].gflag, Bs[j].gstart, h[(size_t)j + 1].G, M, e3.y,
-                                                    E.corr + (size_t)j * CORR_N);
-                  VR_CHECK_LAUNCH();
-                }
-              }
-              return tail_units(E, nb, cfg.est_nseg, cfg.est_ratioA, h[0].has_nan != 0, nan_b, nl, scores + set0,
-                                score_ld, viol, st, EM == 4 ? E.corr : nullptr);
             }
+            return tail_units(E, nb, cfg.est_nseg, cfg.est_ratioA, h[0].has_nan != 0, nan_b, nl, scores + set0,
+                              score_ld, viol, st, EM == 4 ? E.corr : nullptr);
           };
           // EST 3 needs every lane to hold k stimuli: the pass holding the full set runs EST 4
           const bool full0 = full_first && p == 0;
-          if (tri)
-            VR_TRY(full0 ? run_pass(std::integral_constant<int, 6>{}) : run_pass(std::integral_constant<int, 5>{}));
-          else
-            VR_TRY(cfg.est_mode == 3   ? (full0 ? run_pass(std::integral_constant<int, 4>{})
-                                                : run_pass(std::integral_constant<int, 3>{}))
-                   : cfg.est_mode == 2 ? run_pass(std::integral_constant<int, 2>{})
-                                       : run_pass(std::integral_constant<int, 1>{}));
+          VR_TRY(cfg.est_mode == 3 ? (full0 ? run_pass(std::integral_constant<int, 4>{})
+                                            : run_pass(std::integral_constant<int, 3>{}))
+                                   : run_pass(std::integral_constant<int, 1>{}));
         }
       }
       return VR_OK;
@@ -2448,11 +2111,11 @@ static int run_engine_multi_impl(const PlanView& A, const PlanView* Bs, int64_t 
       if ((flags[(size_t)(p - p0)] & 3u) == 2u) g_est_tail_flags.fetch_add(1);
       if (second != JOIN_CHUNK) VR_TRY(join(JOIN_CHUNK));
       g_est_reruns.fetch_add(1);
-      const int64_t set0 = p * sub;
-      const int nl = (int)std::min<int64_t>(sub, total - set0);
+      const int64_t set0 = p * lw;
+      const int nl = (int)std::min<int64_t>(lw, total - set0);
       VR_TRY(with_pass_tag(cfg.use_lds, lw == LANES, narrow, [&](auto tag) { return exact_pass(tag, set0, nl); }));
     }
-    if (p0 == pfirst && flags[0] && p1 < npass) return exact_from(p1 * sub);  // give up on the estimate
+    if (p0 == pfirst && flags[0] && p1 < npass) return exact_from(p1 * lw);  // give up on the estimate
   }
   return VR_OK;
 }
@@ -2511,114 +2174,6 @@ static bool grid_masks_lds(int64_t n) {
   return (size_t)n * sizeof(uint64_t) <= 160 * 1024 - 1024 && env_int("VISREPS_ENGINE_GRID_LDS", 1) != 0;
 }
 
-template <bool LDS>
-static int launch_gridx(int R, unsigned grid, size_t lds, const PlanView& B, const uint64_t* masks, int64_t n,
-                        const GridX& g, uint32_t ns, uint32_t L, uint32_t Lm, uint32_t nch, const uint32_t* segpos,
-                        uint32_t* q, hipStream_t st) {
-  VR_ONCE(VR_TRY(allow_big_lds(k_rankB_gridx<2, LDS>)); VR_TRY(allow_big_lds(k_rankB_gridx<3, LDS>));
-          VR_TRY(allow_big_lds(k_rankB_gridx<4, LDS>)));
-  if (R == 2)
-    k_rankB_gridx<2, LDS><<<grid, ENG_THREADS, lds, st>>>(B.codes, B.gflag, masks, n, g, ns, L, Lm, nch, segpos, q);
-  else if (R == 3)
-    k_rankB_gridx<3, LDS><<<grid, ENG_THREADS, lds, st>>>(B.codes, B.gflag, masks, n, g, ns, L, Lm, nch, segpos, q);
-  else
-    k_rankB_gridx<4, LDS><<<grid, ENG_THREADS, lds, st>>>(B.codes, B.gflag, masks, n, g, ns, L, Lm, nch, segpos, q);
-  VR_CHECK_LAUNCH();
-  return VR_OK;
-}
-
-// A region a grid call can walk in the exact grid form: u16 chunk-relative ranks (every A
-// chunk span, < L + its largest tie group, <= 32767) and 64-bit tie sums (groups < 2^16)
-static bool gridx_region_ok(const PlanHeader& h) {
-  return (uint64_t)PLAN_L + h.max_group <= 32767u && h.max_group < 65536u;
-}
-
-// Every pass of regions rs (2..4 of them, gridx_region_ok; B tie groups < 2^16) in the exact
-// chunk-base form, region-fused: per pass the masks once, each region's exact A walk
-// (pass_a: TB, chunk bases), then one k_rankB_gridx launch per B plan for all of them, then
-// each region's tail. B segments: cfg.nwaves per plan (the exact A side's count, so the tail
-// pairs them as the per-region exact calls do). E: the grid's workspaces (E[r].masks = the
-// shared masks); region 0's B segment tables and queue counters are rewritten.
-static int grid_exact(const PlanView* As, const std::vector<int>& rs, const PlanView* Bs, int64_t nb, int64_t n,
-                      const int32_t* idx, int64_t k, int64_t n_sets, int full_first, double* scores,
-                      int64_t score_ld, uint32_t* const* const* joins, const std::vector<EngineWs>& E,
-                      const std::vector<PlanHeader>& hA, const std::vector<char>& nan_b, const EngineCfg& cfg,
-                      hipStream_t st) {
-  const int64_t M = pairs_of(n);
-  const int64_t total = n_sets + (full_first ? 1 : 0);
-  const int RA = (int)rs.size();
-  VR_REQUIRE(RA >= 2 && RA <= 4, "grid_exact: %d regions", RA);
-  const uint32_t nch = plan_nchunks(M), L = plan_chunk_len(M);
-  const uint32_t Lm = (uint32_t)(((uint64_t)1 << 32) / L);
-  const uint32_t nsx = (uint32_t)cfg.nwaves;
-  VR_REQUIRE(E[0].segstride >= (size_t)nsx + 1 && E[0].useg >= (size_t)nsx * LANES, "grid_exact: segment tables");
-  for (int64_t j = 0; j < nb; ++j) {
-    k_seg_table<<<(nsx + 256) / 256, 256, 0, st>>>(Bs[j].gstart, Bs[j].hdr, M, nsx,
-                                                    E[0].segposB + E[0].segstride * (size_t)j);
-    VR_CHECK_LAUNCH();
-  }
-  for (int r : rs) VR_CHECK_HIP(hipMemsetAsync(E[(size_t)r].viol + EST_MAX_PASSES, 0, sizeof(uint32_t), st));
-  const unsigned ggrid = (unsigned)num_cus();
-  const bool glds = grid_masks_lds(n);
-  // regions per launch: all, or (VISREPS_ENGINE_GRIDX_MAXR < 4, A/B) 4 regions as 2 + 2
-  const int maxr = (RA == 4 && env_int("VISREPS_ENGINE_GRIDX_MAXR", 4) < 4) ? 2 : RA;
-  const int64_t npass = (total + LANES - 1) / LANES;
-  for (int64_t p = 0; p < npass; ++p) {
-    const int64_t set0 = p * LANES;
-    const int nl = (int)std::min<int64_t>(LANES, total - set0);
-    VR_TRY(build_pass_masks(idx, k, set0, nl, full_first, E[0].masks, n, st));
-    for (int r : rs) {
-      const EngineWs& e = E[(size_t)r];
-      VR_TRY((cfg.use_lds ? pass_a<true, true, uint16_t, false>(As[r], n, e, LANES, cfg, st)
-                          : pass_a<false, true, uint16_t, false>(As[r], n, e, LANES, cfg, st)));
-      // the chunk starts go to lpA, dead once pass_a has turned it into baseA
-      k_chunk_starts<<<(nch + 255) / 256, 256, 0, st>>>(As[r].gstart, As[r].chunk_g, nch, e.lpA);
-      VR_CHECK_LAUNCH();
-    }
-    VR_CHECK_HIP(hipMemsetAsync(E[0].queue + QS_RANKB, 0,
-                                sizeof(uint32_t) * (size_t)std::min<int64_t>(nb, QSLOTS - QS_RANKB), st));
-    for (int64_t j = 0; j < nb; ++j) {
-      const uint32_t* segpos = E[0].segposB + E[0].segstride * (size_t)j;
-      for (int i0 = 0; i0 < RA; i0 += maxr) {  // region groups of <= maxr per launch
-        const int ri = std::min(maxr, RA - i0);
-        GridX g{};
-        for (int i = 0; i < ri; ++i) {
-          const int r = rs[(size_t)(i0 + i)];
-          const EngineWs& e = E[(size_t)r];
-          const size_t us = e.useg * (size_t)j;
-          g.TB[i] = static_cast<const uint16_t*>(e.TB);
-          g.posA[i] = joins[r][2 * j];
-          g.base[i] = e.baseA;
-          g.cst[i] = e.lpA;
-          g.seg_tot[i] = e.segB_tot + us;
-          g.seg_part[i] = e.segB_part + us * PB_N;
-        }
-        uint32_t* q = E[0].queue + QS_RANKB + (size_t)(j * 2 + i0 / maxr) % (size_t)(QSLOTS - QS_RANKB);
-        VR_CHECK_HIP(hipMemsetAsync(q, 0, sizeof(uint32_t), st));
-        KtScope kt(KT_RANKB_GRIDX, (double)M * ri, st);
-        if (glds)
-          VR_TRY(launch_gridx<true>(ri, ggrid, (size_t)n * sizeof(uint64_t), Bs[j], E[0].masks, n, g, nsx, L, Lm, nch,
-                                    segpos, q, st));
-        else
-          VR_TRY(launch_gridx<false>(ri, ggrid, 0, Bs[j], E[0].masks, n, g, nsx, L, Lm, nch, segpos, q, st));
-      }
-    }
-    for (int r : rs)
-      VR_TRY(tail_units(E[(size_t)r], nb, nsx, 1u, hA[(size_t)r].has_nan != 0, nan_b, nl,
-                        scores + (size_t)r * nb * score_ld + set0, score_ld, E[(size_t)r].viol + EST_MAX_PASSES, st));
-  }
-  for (int r : rs) {  // an exact pass that breaks the invariants is an error, as in run_engine_multi
-    uint32_t bad = 0;
-    VR_CHECK_HIP(hipMemcpyAsync(&bad, E[(size_t)r].viol + EST_MAX_PASSES, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    VR_CHECK_HIP(hipStreamSynchronize(st));
-    if (bad) {
-      set_error("bootstrap engine: an exact grid pass broke the rank-sum invariants (included pairs / sum of ranks)");
-      return VR_EINTERNAL;
-    }
-  }
-  return VR_OK;
-}
-
 static int run_engine_grid(const PlanView* As, int R, const PlanView* Bs, int64_t nb, int64_t n, const int32_t* idx,
                            int64_t k, int64_t n_sets, int full_first, double* scores, int64_t score_ld,
                            uint32_t* const* const* joins, const EngineWs* Es, const EngineCfg& cfg, hipStream_t st) {
@@ -2626,14 +2181,11 @@ static int run_engine_grid(const PlanView* As, int R, const PlanView* Bs, int64_
   const int64_t total = n_sets + (full_first ? 1 : 0);
   std::vector<int> solo;  // regions run on their own once the fused passes are done
   std::vector<std::vector<int64_t>> fix((size_t)R);  // fused regions' flagged passes (re-run exact)
-  std::vector<int> xg;  // regions walked together in the exact grid form (grid_exact), before the solos
   std::vector<PlanHeader> hA((size_t)R), hB((size_t)nb);
   std::vector<char> nan_b((size_t)nb);
   std::vector<EngineWs> E(Es, Es + R);  // the masks of a pass are built once (region 0's buffer)
   for (int r = 1; r < R; ++r) E[(size_t)r].masks = E[0].masks;
   auto finish = [&]() -> int {
-    if (!xg.empty())
-      VR_TRY(grid_exact(As, xg, Bs, nb, n, idx, k, n_sets, full_first, scores, score_ld, joins, E, hA, nan_b, cfg, st));
     for (int r : solo)
       VR_TRY(run_engine_multi(As[r], Bs, nb, n, idx, k, n_sets, full_first, scores + (size_t)r * nb * score_ld,
                               score_ld, joins[r], Es[0], LANES, cfg, st));
@@ -2645,8 +2197,7 @@ static int run_engine_grid(const PlanView* As, int R, const PlanView* Bs, int64_
   };
   auto all_solo = [&]() -> int {
     solo.clear();
-    for (int r = 0; r < R; ++r)
-      if (std::find(xg.begin(), xg.end(), r) == xg.end()) solo.push_back(r);
+    for (int r = 0; r < R; ++r) solo.push_back(r);
     return finish();
   };
   if (total == 0 || nb == 0 || M == 0) return all_solo();
@@ -2658,35 +2209,11 @@ static int run_engine_grid(const PlanView* As, int R, const PlanView* Bs, int64_
   for (int64_t j = 0; j < nb; ++j) nan_b[(size_t)j] = hB[(size_t)j].has_nan != 0;
   bool b_small = true;  // B tie groups < 2^16 (the fused walks' 64-bit tie sums)
   for (int64_t j = 0; j < nb; ++j) b_small = b_small && hB[(size_t)j].max_group < 65536u;
-  // the exact grid form (opt-in, VISREPS_ENGINE_GRIDX=1): measured slower than the per-region
-  // exact calls on the bench RDMs (36.2-36.9 against 33.8 ms per unit, every pass exact,
-  // profiles/r6_exact_grid_ab.log): one 16-wave workgroup per CU, which the LDS masks and
-  // 128 VGPRs allow, cannot keep the two gathers per pair and region in flight that the
-  // per-region walks' two workgroups per CU do
-  const bool gridx = b_small && R >= 2 && R <= 4 && env_int("VISREPS_ENGINE_GRID", 1) != 0 &&
-                     env_int("VISREPS_ENGINE_GRIDX", 0) != 0;
-  auto take_exact_grid = [&](const std::vector<int>& rs) -> std::vector<int> {  // -> the regions left over
-    std::vector<int> ok, rest;
-    for (int r : rs) (gridx && gridx_region_ok(hA[(size_t)r]) ? ok : rest).push_back(r);
-    if (ok.size() >= 2)
-      xg.insert(xg.end(), ok.begin(), ok.end());
-    else
-      rest.insert(rest.end(), ok.begin(), ok.end());
-    std::sort(xg.begin(), xg.end());
-    return rest;
-  };
-  if (!engine_est()) {  // every pass exact: the exact grid where it applies
-    std::vector<int> all;
-    for (int r = 0; r < R; ++r) all.push_back(r);
-    take_exact_grid(all);
-    return all_solo();
-  }
-  bool fused = cfg.est_mode == 3 && R >= 2 && R <= 4 && env_int("VISREPS_ENGINE_TRI", 0) == 0 &&
-               env_int("VISREPS_ENGINE_LO_JOIN", 0) == 0 && env_int("VISREPS_ENGINE_GRID", 1) != 0;
+  if (!engine_est()) return all_solo();  // every pass exact: the per-region calls
+  const bool fused = cfg.est_mode == 3 && R >= 2 && R <= 4 && env_int("VISREPS_ENGINE_GRID", 1) != 0 && b_small;
   // test hook (vr_test_engine_inject): the first fused region's TB gets the B-side error after
   // its A walk of that pass, so the region must be flagged and re-run on its own
   const int64_t inject = g_test_inject.load(std::memory_order_relaxed);
-  fused = fused && b_small;
   if (!fused) return all_solo();
   std::vector<int> act;  // the fused regions
   for (int r = 0; r < R; ++r) (hA[(size_t)r].max_group < 65536u ? act : solo).push_back(r);
@@ -2694,7 +2221,6 @@ static int run_engine_grid(const PlanView* As, int R, const PlanView* Bs, int64_
   // EST 4 shift is at most 1 -- with k's window instead a group of > 3 tied pairs could
   // shift below 1 and flag the pass)
   const uint2 e3 = est3_params(n_sets > 0 ? k : n, M);
-  const uint2 trip = make_uint2(0u, 0u);
   const uint32_t ns = cfg.est_nseg, nsA = cfg.est_nsegA;
   // A-side walks: masks in LDS when two 16-wave workgroups per CU hold them (n <= 10,176),
   // else from L2 (the per-region calls' choice, engine_cfg)
@@ -2723,15 +2249,9 @@ static int run_engine_grid(const PlanView* As, int R, const PlanView* Bs, int64_
       (bad ? pbad : keep).push_back(r);
     }
     act.swap(keep);
-    // Regions off the estimate go to the exact form (run_engine_multi's choice while the exact
-    // walks keep their masks in LDS; above that EST 1 serves them on their own): two or more of
-    // them walk it region-fused
-    if (cfg.use_lds || env_int("VISREPS_ENGINE_EST1_FALLBACK", 1) == 0) {
-      for (int r : take_exact_grid(pbad)) solo.push_back(r);
-      g_est_predicted.fetch_add((int64_t)xg.size());
-    } else {
-      for (int r : pbad) solo.push_back(r);
-    }
+    // Regions off the estimate run on their own, where run_engine_multi repeats the check,
+    // counts it and picks the exact form or EST 1
+    for (int r : pbad) solo.push_back(r);
   }
   if (act.size() < 2) return all_solo();  // fusing pays with two regions or more
   const int64_t npass = (total + LANES - 1) / LANES;
@@ -2750,8 +2270,8 @@ static int run_engine_grid(const PlanView* As, int R, const PlanView* Bs, int64_
       uint32_t* viol = E[(size_t)r].viol + vslot;
       VR_TRY(est_a([&](auto cl) -> int {
         constexpr bool CL = decltype(cl)::value;
-        return full0 ? pass_a_est<4, CL, true, false>(As[r], n, E[(size_t)r], LANES, nl, cfg, e3, trip, viol, st)
-                     : pass_a_est<3, CL, true, false>(As[r], n, E[(size_t)r], LANES, nl, cfg, e3, trip, viol, st);
+        return full0 ? pass_a_est<4, CL, true, false>(As[r], n, E[(size_t)r], LANES, nl, cfg, e3, viol, st)
+                     : pass_a_est<3, CL, true, false>(As[r], n, E[(size_t)r], LANES, nl, cfg, e3, viol, st);
       }));
       if (p == inject && r == act[0]) {
         k_inject_tb<<<1, LANES, 0, st>>>(static_cast<uint16_t*>(E[(size_t)r].TB), (uint32_t)(M / 2), LANES, nl);

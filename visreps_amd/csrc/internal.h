@@ -96,10 +96,10 @@ __device__ inline uint32_t f32_sort_key(float f) {
 // before and after the one launch it brackets; vr_ktimer_read resolves them.
 namespace vr {
 enum KtKernel : int {
-  KT_RANKB_EST = 0,   // k_rankB, EST forms over bootstrap subsets (EST 3; the probe forms 1/2)
+  KT_RANKB_EST = 0,   // k_rankB, EST forms over bootstrap subsets (EST 3; the table form EST 1)
   KT_RANKB_EXACT = 1, // k_rankB, exact chunk-base form (VISREPS_ENGINE_EST=0, flagged reruns)
   KT_RANKA = 2,       // k_rankA (both forms)
-  KT_JOIN = 3,        // k_join / k_join_lo
+  KT_JOIN = 3,        // k_join: a unit's A positions (and, for the exact form, A chunks)
   KT_GRAM_WIDE = 4,   // k_gram3p / k_gram3w (256^2 super-tiles)
   KT_GRAM_TILE = 5,   // k_gram3 / k_gram (128^2 tiles)
   KT_COUNTA = 6,      // k_countA
@@ -109,8 +109,7 @@ enum KtKernel : int {
   KT_JOIN4 = 10,      // k_join4: shared join of one B plan to up to 4 A plans (units = algorithmic bytes)
   KT_FULL_CORR = 11,  // k_full_corr: lane 0's shift sums of an EST 4 pass, per unit (4 B / pair streamed)
   KT_RANKB_GRID = 12,  // k_rankB_grid: one B plan x up to 4 regions, EST 3 (units: pairs x regions)
-  KT_RANKB_GRIDX = 13, // k_rankB_gridx: the same in the exact chunk-base form (units: pairs x regions)
-  KT_N = 14
+  KT_N = 13
 };
 bool ktimer_on();
 struct KtScope {

@@ -659,55 +659,42 @@ def engine_bytes(n: int, n_boot: int) -> float:
 # codes and the two join arrays (posA, chunkA) and gathers one TB row per pair (its 256-byte
 # chunk-base rows come from a 2 MB L2-resident table, not HBM). EST form (the default): the
 # A side streams its codes twice (count pre-pass + rank walk); the B walk streams its codes
-# and the A positions and computes the window low ends from them (VISREPS_ENGINE_LO_JOIN=1:
-# the join also writes the low ends -- 4 B more per pair there -- which the prefetching EST 3/4
-# walk does not read); k_join reads the B codes, gathers the 4-B A position map and writes
-# the A positions, per unit.
+# and the A positions and computes the window low ends from them; k_join reads the B codes,
+# gathers the 4-B A position map and writes the A positions, per unit.
 def engine_tri(n: int, est: Optional[bool] = None) -> bool:
-    """Whether the bootstrap calls at n stimuli run the triangle-order EST passes (EST 5/6:
-    M <= 2^28, EST 3 estimate, opt-in VISREPS_ENGINE_TRI=1; engine.hip run_engine_multi_impl)."""
-    import os
-
-    if est is None:
-        est = os.environ.get("VISREPS_ENGINE_EST") != "0"
-    return (est and os.environ.get("VISREPS_ENGINE_TRI", "0") != "0"
-            and os.environ.get("VISREPS_ENGINE_EST_MODE", "3") == "3" and n * (n - 1) // 2 <= (1 << 28))
+    # The triangle-order EST passes were removed from the engine; bench.py still
+    # asks whether a run uses them, so the answer stays here.
+    return False
 
 
 def engine_pair_bytes(est: Optional[bool] = None, tri: bool = False) -> Tuple[int, int, int]:
-    """(A walk per pass, B walk per pass and unit, join per unit) bytes per pair."""
+    """(A walk per pass, B walk per pass and unit, join per unit) bytes per pair. `tri` is
+    accepted for bench.py's call and ignored (see engine_tri)."""
     import os
 
     if est is None:
         est = os.environ.get("VISREPS_ENGINE_EST") != "0"
-    if est and tri:
-        # triangle-order TB: A: codes 4 (count pre-pass) + codes 4 + TB row write 128 (at the
-        # pair's triangle index); B: codes 4 + TB row gather 128; no join
-        return 4 + 4 + 128, 4 + 128, 0
     if not est:
         # A: codes 4 + TB row write 128; B: codes, posA, chunkA 4 each + TB row 128;
         # join: B codes 4 + 8-B pair-map record + posA and chunkA writes 4 each
         return 4 + 128, 4 + 4 + 4 + 128, 4 + 8 + 4 + 4
-    lo = 4 if os.environ.get("VISREPS_ENGINE_LO_JOIN", "0") != "0" else 0
     # A: codes 4 (count pre-pass) + codes 4 + TB row write 128; B: codes 4 + posA 4
-    # (+ low end) + TB row gather 128; join: B codes 4 + position-map gather 4 + posA write 4
-    # (+ low-end write)
-    return 4 + 4 + 128, 4 + 4 + lo + 128, 4 + 4 + 4 + lo
+    # + TB row gather 128; join: B codes 4 + position-map gather 4 + posA write 4
+    return 4 + 4 + 128, 4 + 4 + 128, 4 + 4 + 4
 
 
 def engine_call_bytes(n: int, subsets: int, units: int, joined: bool = False) -> float:
     """Algorithmic HBM bytes of one engine call: `units` B plans against one A plan over
-    `subsets` subsets (64 per pass; 63 in the triangle-order form); joined: the units' joins
-    were done beforehand (SharedJoins, counted by shared_join_bytes)."""
-    tri = engine_tri(n)
-    a, b, j = engine_pair_bytes(tri=tri)
+    `subsets` subsets (64 per pass); joined: the units' joins were done beforehand
+    (SharedJoins, counted by shared_join_bytes)."""
+    a, b, j = engine_pair_bytes()
     if joined:
         j = 0
     M = n * (n - 1) // 2
-    passes = -(-subsets // (63 if tri else 64))
+    passes = -(-subsets // 64)
     # + the full-set pass's lane-0 shift sums (k_full_corr: the A positions again, 4 B per pair
     # and unit; csrc/engine.hip est4_shift)
-    return float(M) * (passes * (a + units * b) + units * j + (0 if tri else 4 * units))
+    return float(M) * (passes * (a + units * b) + units * j + 4 * units)
 
 
 def run_unit(plan_m: R.RankPlan, plan_n: R.RankPlan, idx: Optional[np.ndarray],
@@ -729,10 +716,7 @@ def engine_grid_bytes(n: int, subsets: int, regions: int, units_per_region: int)
     """Algorithmic HBM bytes of one grid call (bootstrap_spearman_grid, every unit joined):
     per region its A side as engine_call_bytes; per pass and B plan one walk for all regions,
     the B codes once (4 B per pair) and per region the A position (4) and the TB row (128)."""
-    tri = engine_tri(n)
-    if tri:  # (the grid form has no triangle-order variant: the per-region calls)
-        return regions * engine_call_bytes(n, subsets, units_per_region, joined=True)
-    a, b, _ = engine_pair_bytes(tri=False)
+    a, b, _ = engine_pair_bytes()
     M = n * (n - 1) // 2
     passes = -(-subsets // 64)
     walk = 4 + regions * (b - 4)  # codes once, then per region A position + TB row
