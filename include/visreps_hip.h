@@ -106,7 +106,9 @@ int vr_gram_f32(const float* X, int64_t n, int64_t d, int64_t ldx, float* G, int
 /* Encoding-score statistic (visreps/analysis/encoding_score.py:206-224): for each of
  * `draws` row subsets (idx [dev] int32 draws x k; null = all n rows, draws = 1) the mean
  * over the v columns of the per-column Pearson r between Y and P (himalaya 0.4.9
- * correlation_score: zscore products, population std; zero variance -> NaN), in fp64.
+ * correlation_score: zscore products, population std), in fp64. An exactly constant column
+ * of Y or P, whatever its value, or a non-finite entry among a draw's rows gives NaN for
+ * that column and for the draw's score.
  * Y, P [dev] fp32 (n, v) row-major with leading dimension ld. voxel_r [dev] fp64
  * (draws, v) or null. Workspace: vr_corr_score_workspace(v, draws). */
 size_t vr_corr_score_workspace(int64_t v, int64_t draws);
@@ -516,7 +518,9 @@ int vr_mean_from_sum_f32(const float* sum, int64_t p, int64_t n, float* mean, vo
 /* cov [dev] fp64 (p, p), leading dimension ldc: sum over rows of
  * ((double)x - (double)mean)^T ((double)x - (double)mean) / denom, exactly symmetric, on
  * the fp64 MFMA. mean [dev] fp32 p. denom = n - 1 for the reference's covariance, 1 for a
- * rank's partial sum (multi-GPU: all-reduce, then divide). */
+ * rank's partial sum (multi-GPU: all-reduce, then divide). n = 0 (a rank with an empty
+ * shard) is accepted: cov is all zeros, and vr_pca_cov_workspace(0, p) is the size of that
+ * launch, as for every accepted (n, p). */
 size_t vr_pca_cov_workspace(int64_t n, int64_t p);
 int vr_pca_cov_f64(const float* X, int64_t n, int64_t p, int64_t ldx, const float* mean,
                    double denom, double* cov, int64_t ldc, void* ws, size_t ws_bytes,

@@ -92,7 +92,30 @@ def _worker(rank, world, port, x, bounds, out):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("world,bounds", [(2, [0, 700, 1500]), (3, [0, 1, 900, 1500])])
+def _cov_tile_bytes(p):
+    """One slice of k_cov's partials: every 64 x 64 fp64 tile of the upper triangle, which
+    each workgroup stores whole whatever the row count."""
+    t = -(-p // 64)
+    return t * (t + 1) // 2 * 64 * 64 * 8
+
+
+@pytest.mark.parametrize("p", [3, 64, 65, 1000, 4096])
+def test_cov_workspace_covers_an_empty_shard(p):
+    # vr_pca_cov_f64 accepts n = 0 (a rank whose shard is empty) and launches one slice of
+    # zero stages: the size function must report that slice, not a token 256 bytes
+    from visreps_amd._lib import lib
+
+    L = lib()
+    empty, one = L.vr_pca_cov_workspace(0, p), L.vr_pca_cov_workspace(1, p)
+    assert empty >= _cov_tile_bytes(p), (p, empty, _cov_tile_bytes(p))
+    assert empty >= one, (p, empty, one)
+    for n in (1, 16, 17, 5000):  # and every launch has at least one slice
+        assert L.vr_pca_cov_workspace(n, p) >= _cov_tile_bytes(p)
+
+
+# bounds: an ordinary split, a one-row shard, an empty shard in the middle, an empty first rank
+@pytest.mark.parametrize("world,bounds", [(2, [0, 700, 1500]), (3, [0, 1, 900, 1500]),
+                                          (3, [0, 700, 700, 1500]), (3, [0, 0, 700, 1500])])
 def test_sharded_pca_gloo_matches_oracle(world, bounds):
     x = _feats(1500, 40, seed=3, scale=11.0)
     mgr = mp.get_context("spawn").Manager()
@@ -180,3 +203,82 @@ def test_sharded_pca_world1_on_device(dev):
         dist.destroy_process_group()
     c1, v1, m1, t1 = C.batched_pca(x, 6)
     assert np.array_equal(mean, m1) and np.array_equal(vals, v1) and np.array_equal(comps, c1)
+
+
+@pytest.mark.gpu
+def test_empty_shard_on_device(dev):
+    # what batched_pca_sharded runs on a rank without rows: the column sum passes its init
+    # through, the covariance partial is zero and adds nothing, and nothing is written
+    # outside the output and a workspace of exactly the size the library asked for
+    from visreps_amd import coarsegrain as C
+    from visreps_amd._lib import lib, workspace
+
+    n, p = 1000, 130
+    x = _feats(n, p, seed=9, scale=5.0)
+    xt = torch.from_numpy(x).to(dev)
+    s = C.col_sum(xt[:400])
+    assert torch.equal(C.col_sum(xt[:0], s).view(torch.int32), s.view(torch.int32))
+    assert torch.equal(C.col_sum(xt[400:400], s).view(torch.int32), s.view(torch.int32))
+    mean = C.mean_from_sum(C.col_sum(xt), n)
+    assert np.array_equal(mean.cpu().numpy(), x.mean(axis=0))
+
+    need = lib().vr_pca_cov_workspace(0, p)
+    assert need >= _cov_tile_bytes(p)  # checked before the launch: its tiles must fit
+    workspace.release("pca_cov")
+    guard = torch.full((4096,), 0xA5, dtype=torch.uint8, device=dev)
+    zero = C.cov_sum(xt[:0], mean, 1.0)
+    torch.cuda.synchronize(dev)
+    assert workspace.current(dev, "pca_cov") == max(need, 256)
+    assert bool((guard == 0xA5).all())
+    assert zero.shape == (p, p) and bool((zero == 0).all())
+
+    a, b = C.cov_sum(xt[:400], mean, 1.0), C.cov_sum(xt[400:], mean, 1.0)
+    workspace.release("pca_cov")
+    mid = C.cov_sum(xt[400:400], mean, 1.0)
+    assert bool((mid == 0).all())
+    assert torch.equal(((a + mid) + b).view(torch.int64), (a + b).view(torch.int64))
+    d = x.astype(np.float64) - mean.cpu().numpy().astype(np.float64)
+    ref = d.T @ d
+    err, scale = float(np.max(np.abs((a + mid + b).cpu().numpy() - ref))), float(np.abs(ref).max())
+    print(f"empty shard: max |err| / scale = {err / scale:.3e} (tol 1e-12)")
+    assert err <= 1e-12 * scale
+
+
+def _nan_padded_view(x, kind, dev):
+    """x (n, p) as a view of a wider NaN-filled device buffer. "offset": columns 1..p of a
+    buffer whose pitch is a multiple of 4, so the base pointer is one float off 16-byte
+    alignment; "odd": columns 0..p-1 of a buffer with an odd pitch."""
+    n, p = x.shape
+    ld, c0 = ((p + 8) // 4 * 4, 1) if kind == "offset" else ((p + 3) | 1, 0)
+    big = torch.full((n, ld), float("nan"), dtype=torch.float32, device=dev)
+    big[:, c0:c0 + p] = torch.from_numpy(x).to(dev)
+    view = big[:, c0:c0 + p]
+    assert view.stride(0) == ld and (ld % 4 == 0) == (kind == "offset") and view.data_ptr() % 16 == 4 * c0
+    return view
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["offset", "odd"])
+@pytest.mark.parametrize("p", [63, 64, 65, 130])
+def test_mean_cov_on_strided_views(dev, p, kind):
+    # rows below, at and above the 16-row stage, and 2049 rows: two row slices, the second
+    # ragged. The padding is NaN: one read past a row's p columns poisons the result.
+    from visreps_amd import coarsegrain as C
+
+    for n in (1, 15, 16, 17, 2049):
+        x = _feats(n, p, seed=10 + n, scale=3.0)
+        view = _nan_padded_view(x, kind, dev)
+        if n > 1:
+            mean, cov = C.pca_mean_cov(view)
+        else:  # n - 1 = 0: the same two kernels with denominator 1
+            mean = C.mean_from_sum(C.col_sum(view), n)
+            cov = C.cov_sum(view, mean, 1.0)
+        assert np.array_equal(mean.cpu().numpy(), x.mean(axis=0))
+        got = cov.cpu().numpy()
+        d = x.astype(np.float64) - x.mean(axis=0).astype(np.float64)
+        ref = (d.T @ d) / max(n - 1, 1)
+        scale = float(np.abs(ref).max())
+        err = float(np.max(np.abs(got - ref)))
+        print(f"{kind} view n={n} p={p}: max |err| = {err:.3e}, scale = {scale:.3e} (tol 1e-12 of scale)")
+        assert np.array_equal(got, got.T)
+        assert err <= 1e-12 * scale

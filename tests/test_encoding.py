@@ -6,6 +6,8 @@ kernel and its bootstrap (vr_corr_score_f32), the dual-form RidgeCV and the whol
 compute_encoding_score flow against the oracle's primal-form restatement. The alpha
 selection rule is restated from himalaya 0.4.9 (not installed): parity unpinned beyond
 this oracle."""
+import functools
+
 import numpy as np
 import pytest
 import scipy.stats
@@ -141,6 +143,270 @@ def test_corr_score_constant_column_is_nan(dev):
     P[:, 1] = 2.0
     s = corr_score(torch.from_numpy(Y).to(dev), torch.from_numpy(P).to(dev))
     assert np.isnan(s)
+
+
+# ------------------------------------------------------- vr_corr_score_f32 at its edges
+# k_corr_cols: 256 columns per workgroup, the draw's row indices staged 4096 per LDS round,
+# five fp64 moments per column of the data shifted by the column's value in the draw's
+# first row. The yardstick is a numpy fp64 two-pass Pearson per column (_ref_corr) at the
+# file's 1e-10; the oracle's own error on offset data is checked against it on the CPU.
+CORR_TOL = 1e-10
+CONSTANTS = [np.float32(c) for c in (0.1, 0.3, 1e-3, 123.456, -7.7)]
+
+
+def _ref_corr(Y, P):
+    """Per-column two-pass fp64 Pearson r; NaN for an exactly constant or non-finite column."""
+    Y, P = np.asarray(Y, np.float64), np.asarray(P, np.float64)
+    with np.errstate(all="ignore"):
+        dy, dp = Y - Y.mean(0), P - P.mean(0)
+        r = (dy * dp).sum(0) / np.sqrt((dy * dy).sum(0) * (dp * dp).sum(0))
+    dead = np.all(Y == Y[0], axis=0) | np.all(P == P[0], axis=0)
+    return np.where(dead | ~np.isfinite(r), np.nan, r)
+
+
+def _moments_restated(Y, P, pivot):
+    """k_corr_cols' arithmetic in numpy: sequential fp64 sums in row order, variances from
+    the raw moments. pivot=False is the one-pass form the kernel used to take on the data as
+    read; pivot=True subtracts each column's first-row value in fp64 first. (The kernel
+    contracts y * y into FMAs, so its bits differ; the mechanism is the same.)"""
+    Y, P = np.asarray(Y, np.float64), np.asarray(P, np.float64)
+    if pivot:
+        Y, P = Y - Y[0], P - P[0]
+    k = float(Y.shape[0])
+    sy = sp = syy = spp = syp = np.zeros(Y.shape[1])
+    for y, p in zip(Y, P):
+        sy, sp, syy, spp, syp = sy + y, sp + p, syy + y * y, spp + p * p, syp + y * p
+    my, mp = sy / k, sp / k
+    vy, vp, cov = syy / k - my * my, spp / k - mp * mp, syp / k - my * mp
+    with np.errstate(all="ignore"):
+        return cov / np.sqrt(np.maximum(vy, 0.0) * np.maximum(vp, 0.0))
+
+
+@functools.lru_cache(maxsize=None)
+def _corr_case(n, v, seed):
+    """(Y, P, fp64 reference of all rows), read-only and shared."""
+    _, Y = _data(n, 8, v, seed)
+    P = (Y + np.random.RandomState(seed + 1).randn(n, v)).astype(np.float32)
+    ref = _ref_corr(Y, P)
+    for a in (Y, P, ref):
+        a.setflags(write=False)
+    return Y, P, ref
+
+
+def _choice(n, k, draws, seed):
+    rng = np.random.RandomState(seed)
+    return np.stack([rng.choice(n, k, replace=False) for _ in range(draws)]).astype(np.int32)
+
+
+def _check_corr(what, score, vox, refs):
+    """score(s) and per-voxel r of every draw against refs (draws, v): the same NaN mask,
+    CORR_TOL elsewhere; a draw's score is the mean of its row (NaN if any voxel is)."""
+    vox = vox.cpu().numpy()
+    refs = np.atleast_2d(refs)
+    scores = np.atleast_1d(np.asarray(score, np.float64))
+    assert vox.shape == refs.shape and scores.shape == (refs.shape[0],), (what, vox.shape, refs.shape)
+    ok = ~np.isnan(refs)
+    err_v = float(np.max(np.abs(vox[ok] - refs[ok]))) if ok.any() else 0.0
+    ref_s = refs.mean(axis=1)
+    ok_s = ~np.isnan(ref_s)
+    err_s = float(np.max(np.abs(scores[ok_s] - ref_s[ok_s]))) if ok_s.any() else 0.0
+    print(f"{what}: max |err| voxel = {err_v:.3e}, score = {err_s:.3e} (tol {CORR_TOL:g}), "
+          f"NaN voxels got/ref = {int(np.isnan(vox).sum())}/{int((~ok).sum())}")
+    assert np.array_equal(np.isnan(vox), ~ok), (what, np.argwhere(np.isnan(vox) != ~ok)[:5])
+    assert np.array_equal(np.isnan(scores), ~ok_s), (what, scores)
+    assert err_v <= CORR_TOL and err_s <= CORR_TOL, (what, err_v, err_s)
+
+
+def _constant_inputs():
+    """(where, column, value) of every constant-column case."""
+    return [(w, c, val) for w in ("Y", "P") for c in (0, 256) for val in CONSTANTS]
+
+
+def _with_constant(Y, P, where, col, val):
+    Y, P = Y.copy(), P.copy()
+    (Y if where == "Y" else P)[:, col] = val
+    return Y, P
+
+
+@pytest.mark.parametrize("n", [207, 900])
+def test_constant_column_contract_on_cpu(n):
+    # The oracle scores an exactly constant float32 column NaN whatever its value: the fp64
+    # sum of k <= 2^29 copies of a 24-bit value is exact, so its mean is the value and its
+    # std exactly 0. The kernel's moments restated in numpy agree once every column is shifted
+    # by its first-row value; taken on the data as read (the kernel before the pivot) they
+    # give +-inf or a finite r wherever the value and its square do not sum exactly.
+    Y, P, _ = _corr_case(n, 300, 20)
+    raw_not_nan = 0
+    for where, col, val in _constant_inputs():
+        Yc, Pc = _with_constant(Y, P, where, col, val)
+        with np.errstate(all="ignore"):
+            orc = E.correlation_score(Yc, Pc)
+        assert np.isnan(orc[col]) and int(np.isnan(orc).sum()) == 1 and np.isnan(orc.mean())
+        sl = slice(col, col + 1)
+        assert np.isnan(_moments_restated(Yc[:, sl], Pc[:, sl], pivot=True)[0])
+        raw_not_nan += not np.isnan(_moments_restated(Yc[:, sl], Pc[:, sl], pivot=False)[0])
+    print(f"n={n}: one-pass moments without a pivot miss the NaN in {raw_not_nan} of 20 cases")
+    assert raw_not_nan > 0
+
+
+@pytest.mark.parametrize("shift_y,shift_p", [(1000.0, 1000.0), (0.0, 1e4)])
+def test_offset_data_restated_on_cpu(shift_y, shift_p):
+    # the pivoted moments hold the file's tolerance on offset data; the raw ones do not
+    Y, P, _ = _corr_case(900, 300, 20)
+    Yo, Po = (Y + np.float32(shift_y)).astype(np.float32), (P + np.float32(shift_p)).astype(np.float32)
+    ref = _ref_corr(Yo, Po)
+    piv = float(np.max(np.abs(_moments_restated(Yo, Po, pivot=True) - ref)))
+    raw = float(np.max(np.abs(_moments_restated(Yo, Po, pivot=False) - ref)))
+    orc = float(np.max(np.abs(E.correlation_score(Yo, Po) - ref)))
+    print(f"shift ({shift_y:g}, {shift_p:g}): max |err| pivoted {piv:.3e}, raw {raw:.3e}, oracle {orc:.3e}")
+    assert piv <= CORR_TOL and orc <= CORR_TOL and raw > CORR_TOL
+
+
+def _dev_pair(Y, P, dev):
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(Y)).to(dev), torch.from_numpy(np.ascontiguousarray(P)).to(dev)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,k,draws", [(207, None, 1), (900, None, 1), (230, 207, 5)])
+def test_corr_score_constant_column_any_value_is_nan(dev, n, k, draws):
+    from visreps_amd.analysis.encoding_score import corr_score
+
+    Y, P, ref_all = _corr_case(n, 300, 20)
+    idx = None if k is None else _choice(n, k, draws, 21)
+    refs = ref_all[None, :] if idx is None else np.stack([_ref_corr(Y[i], P[i]) for i in idx])
+    for where, col, val in _constant_inputs():
+        Yc, Pc = _with_constant(Y, P, where, col, val)
+        want = refs.copy()
+        want[:, col] = np.nan  # every other column is untouched: its reference stands
+        s, vox = corr_score(*_dev_pair(Yc, Pc, dev), idx, voxels=True)
+        _check_corr(f"n={n} k={k} {where}[:, {col}] = {val!r}", s, vox, want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shift_y,shift_p", [(1000.0, 1000.0), (0.0, 1e4)])
+@pytest.mark.parametrize("n", [207, 900])
+def test_corr_score_offset_data_keeps_tolerance(dev, n, shift_y, shift_p):
+    from visreps_amd.analysis.encoding_score import corr_score
+
+    Y, P, _ = _corr_case(n, 300, 20)
+    Yo, Po = (Y + np.float32(shift_y)).astype(np.float32), (P + np.float32(shift_p)).astype(np.float32)
+    yt, pt = _dev_pair(Yo, Po, dev)
+    s, vox = corr_score(yt, pt, voxels=True)
+    _check_corr(f"n={n} shift ({shift_y:g}, {shift_p:g}) all rows", s, vox, _ref_corr(Yo, Po))
+    idx = _choice(n, int(0.9 * n), 5, 22)
+    s, vox = corr_score(yt, pt, idx, voxels=True)
+    _check_corr(f"n={n} shift ({shift_y:g}, {shift_p:g}) 5 draws", s, vox,
+                np.stack([_ref_corr(Yo[i], Po[i]) for i in idx]))
+
+
+@pytest.mark.gpu
+def test_corr_score_second_index_round(dev):
+    # the draw's rows are staged 4096 at a time: k = 4096 is one full round, 4097 a second
+    # round of one row, 4500 a ragged second round
+    from visreps_amd.analysis.encoding_score import corr_score
+
+    Y, P, _ = _corr_case(4500, 3, 23)
+    yt, pt = _dev_pair(Y, P, dev)
+    for k in (4096, 4097, 4500):
+        idx = _choice(4500, k, 3, k)
+        s, vox = corr_score(yt, pt, idx, voxels=True)
+        _check_corr(f"n=4500 k={k}", s, vox, np.stack([_ref_corr(Y[i], P[i]) for i in idx]))
+    s, vox = corr_score(yt[:4097], pt[:4097], voxels=True)
+    _check_corr("n=4097 all rows", s, vox, _ref_corr(Y[:4097], P[:4097]))
+
+
+@pytest.mark.gpu
+def test_corr_score_voxels_of_every_draw(dev):
+    # voxel_r is (draws, v): row b of the output is draw b, across both column blocks
+    from visreps_amd.analysis.encoding_score import corr_score
+
+    Y, P, _ = _corr_case(120, 257, 24)
+    idx = _choice(120, 100, 3, 25)
+    s, vox = corr_score(*_dev_pair(Y, P, dev), idx, voxels=True)
+    refs = np.stack([_ref_corr(Y[i], P[i]) for i in idx])
+    assert np.median(np.abs(refs[0] - refs[1])) > 1e-4  # the draws' rows are told apart
+    _check_corr("draws=3 v=257", s, vox, refs)
+
+
+def _corr_entry(yt, pt, n, v, ld, idx, dev):
+    """vr_corr_score_f32 called directly (row pitch ld): (scores, voxel_r) as numpy."""
+    import torch
+    from visreps_amd._lib import check, lib, stream_of
+
+    draws, k = idx.shape
+    it = torch.from_numpy(idx).to(dev)
+    scores = torch.empty(draws, dtype=torch.float64, device=dev)
+    vox = torch.empty((draws, v), dtype=torch.float64, device=dev)
+    L = lib()
+    ws = torch.empty(L.vr_corr_score_workspace(v, draws), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(L.vr_corr_score_f32(yt.data_ptr(), pt.data_ptr(), n, v, ld, it.data_ptr(), k, draws,
+                                  scores.data_ptr(), vox.data_ptr(), ws.data_ptr(), ws.numel(),
+                                  stream_of(dev)), "vr_corr_score_f32")
+    return scores.cpu().numpy(), vox.cpu().numpy()
+
+
+@pytest.mark.gpu
+def test_corr_score_strided_input_equals_contiguous(dev):
+    import torch
+
+    n, v, ld = 120, 257, 262
+    Y, P, _ = _corr_case(n, v, 24)
+    idx = _choice(n, 100, 3, 26)
+    yt, pt = _dev_pair(Y, P, dev)
+    want = _corr_entry(yt, pt, n, v, v, idx, dev)
+    wide = []
+    for t in (yt, pt):
+        buf = torch.full((n, ld), float("nan"), dtype=torch.float32, device=dev)
+        buf[:, :v] = t
+        wide.append(buf)
+    got = _corr_entry(wide[0], wide[1], n, v, ld, idx, dev)
+    assert not np.isnan(got[0]).any() and not np.isnan(got[1]).any()  # the padding is never read
+    assert got[0].tobytes() == want[0].tobytes() and got[1].tobytes() == want[1].tobytes()
+    refs = np.stack([_ref_corr(Y[i], P[i]) for i in idx])
+    err = float(np.max(np.abs(got[1] - refs)))
+    print(f"ld={ld}: max |err| voxel = {err:.3e} (tol {CORR_TOL:g})")
+    assert err <= CORR_TOL
+
+
+@pytest.mark.gpu
+def test_corr_score_unsorted_rows_and_single_row(dev):
+    from visreps_amd.analysis.encoding_score import corr_score
+
+    Y, P, _ = _corr_case(230, 300, 20)
+    yt, pt = _dev_pair(Y, P, dev)
+    idx = _choice(230, 207, 3, 27)
+    assert not np.array_equal(idx, np.sort(idx, axis=1))
+    s_u, v_u = corr_score(yt, pt, idx, voxels=True)
+    s_s, v_s = corr_score(yt, pt, np.sort(idx, axis=1), voxels=True)
+    err = float(np.max(np.abs(v_u.cpu().numpy() - v_s.cpu().numpy())))
+    print(f"unsorted vs sorted rows: max |diff| voxel = {err:.3e}, score = {np.max(np.abs(s_u - s_s)):.3e} "
+          f"(tol {CORR_TOL:g})")
+    assert err <= CORR_TOL and np.max(np.abs(s_u - s_s)) <= CORR_TOL
+    _check_corr("unsorted rows vs fp64", s_u, v_u, np.stack([_ref_corr(Y[i], P[i]) for i in idx]))
+    # one row: every variance is 0, every voxel and the score undefined
+    s1, v1 = corr_score(yt, pt, _choice(230, 1, 3, 28), voxels=True)
+    assert np.isnan(s1).all() and np.isnan(v1.cpu().numpy()).all()
+    s1, v1 = corr_score(yt[:1], pt[:1], voxels=True)
+    assert np.isnan(s1) and np.isnan(v1.cpu().numpy()).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("value", [np.nan, np.inf])
+def test_corr_score_non_finite_input_is_nan(dev, value):
+    # one non-finite entry, in the draw's first row (the pivot) or later: that voxel is NaN
+    from visreps_amd.analysis.encoding_score import corr_score
+
+    Y, P, ref = _corr_case(207, 300, 20)
+    for row in (0, 100):
+        Yc = Y.copy()
+        Yc[row, 256] = value
+        want = ref.copy()
+        want[256] = np.nan
+        s, vox = corr_score(*_dev_pair(Yc, P, dev), voxels=True)
+        _check_corr(f"Y[{row}, 256] = {value}", s, vox, want)
 
 
 @pytest.mark.gpu

@@ -250,6 +250,94 @@ def test_two_pass_subset_entry(dev):
     assert abs(float(out.item()) - _ref64_one(a, b, sub)) <= TOL64
 
 
+def _two_pass(ta, tb, n, ld, sub, dev):
+    """vr_pearson_triu_f32 (sub None) or vr_pearson_triu_subset_f32 called directly with row
+    pitch ld, on a workspace of exactly the size the library asks for."""
+    import torch
+
+    from visreps_amd._lib import check, lib, stream_of
+
+    L = lib()
+    out = torch.empty(1, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        if sub is None:
+            ws = torch.empty(L.vr_pearson_triu_workspace(n), dtype=torch.uint8, device=dev)
+            check(L.vr_pearson_triu_f32(ta.data_ptr(), tb.data_ptr(), n, ld, out.data_ptr(), ws.data_ptr(),
+                                        ws.numel(), stream_of(dev)), "vr_pearson_triu_f32")
+        else:
+            ti = torch.from_numpy(np.ascontiguousarray(sub, dtype=np.int32)).to(dev)
+            ws = torch.empty(L.vr_pearson_triu_subset_workspace(len(sub)), dtype=torch.uint8, device=dev)
+            check(L.vr_pearson_triu_subset_f32(ta.data_ptr(), tb.data_ptr(), n, ld, ti.data_ptr(), len(sub),
+                                               out.data_ptr(), ws.data_ptr(), ws.numel(), stream_of(dev)),
+                  "vr_pearson_triu_subset_f32")
+    return np.array([float(out.item())])
+
+
+def _on_device(m, dev, ld=None):
+    """m on the device, contiguous or as the first n columns of a NaN-filled (n, ld) buffer."""
+    import torch
+
+    t = torch.from_numpy(np.array(m)).to(dev)
+    if ld is None:
+        return t
+    buf = torch.full((m.shape[0], ld), float("nan"), dtype=torch.float32, device=dev)
+    buf[:, :m.shape[1]] = t
+    return buf
+
+
+# k_pearson_rows walks row a's pairs in steps of 256 columns: its second trip needs more than
+# 257 columns. 258: one pair in the second trip of row 0 only; 515: a third trip of one pair;
+# 600: ragged.
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [258, 515, 600])
+def test_two_pass_full_beyond_one_trip(dev, n):
+    a, b = _rdms(n)
+    got = _two_pass(_on_device(a, dev), _on_device(b, dev), n, n, None, dev)
+    full = np.arange(n)
+    _check(got, np.array([_ref64_one(a, b, full)]), TOL64, f"two-pass n={n} vs fp64")
+    _check(got, np.array([O.compute_rdm_correlation(a, b, "Pearson")]), TOL_ORACLE, f"two-pass n={n} vs oracle")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("order", ["sorted", "permuted"])
+@pytest.mark.parametrize("k", [258, 515])
+def test_two_pass_subset_beyond_one_trip(dev, k, order):
+    n = 600
+    a, b = _rdms(n)
+    sub = _draws(n, 1, k=k)[0]  # rng.choice: in no order
+    if order == "sorted":
+        sub = np.sort(sub)
+    else:
+        assert np.any(np.diff(sub) < 0)  # pairs below the diagonal: read at [min, max]
+    got = _two_pass(_on_device(a, dev), _on_device(b, dev), n, n, sub, dev)
+    _check(got, np.array([_ref64_one(a, b, sub)]), TOL64, f"two-pass subset k={k} {order} vs fp64")
+    orc = O.compute_rdm_correlation(a[np.ix_(sub, sub)], b[np.ix_(sub, sub)], "Pearson")
+    _check(got, np.array([orc]), TOL_ORACLE, f"two-pass subset k={k} {order} vs oracle")
+
+
+@pytest.mark.gpu
+def test_two_pass_strided_and_non_finite(dev):
+    n, ld = 300, 307
+    a, b = _rdms(n)
+    sub = _draws(n, 1, k=270)[0]
+    ta, tb = _on_device(a, dev), _on_device(b, dev)
+    wa, wb = _on_device(a, dev, ld), _on_device(b, dev, ld)
+    for s in (None, sub):
+        want, got = _two_pass(ta, tb, n, n, s, dev), _two_pass(wa, wb, n, ld, s, dev)
+        assert got.tobytes() == want.tobytes() and np.isfinite(got).all()  # the padding is never read
+        rows = np.arange(n) if s is None else s
+        _check(got, np.array([_ref64_one(a, b, rows)]), TOL64, f"two-pass ld={ld} subset={s is not None} vs fp64")
+    # one non-finite entry, in a row's second trip of 256 columns: the score is undefined
+    for which, value in (("a", np.nan), ("b", np.inf)):
+        a2, b2 = a.copy(), b.copy()
+        tgt = a2 if which == "a" else b2
+        tgt[3, 280] = tgt[280, 3] = value
+        assert np.isnan(_ref64_one(a2, b2, np.arange(n)))
+        assert np.isnan(_two_pass(_on_device(a2, dev), _on_device(b2, dev), n, n, None, dev)[0])
+        both = np.sort(np.concatenate([[3, 280], np.setdiff1d(sub, [3, 280])]))
+        assert np.isnan(_two_pass(_on_device(a2, dev), _on_device(b2, dev), n, n, both, dev)[0])
+
+
 @pytest.mark.gpu
 def test_deterministic(dev):
     a, b = _rdms(257)

@@ -78,6 +78,41 @@ def test_gpu_projector_matches_host(dev, tmp_path, B, D, k):
     assert np.max(np.abs(got - ref) / scale) < 1e-5
 
 
+def _cycled_csr(k=70, D=100, lengths=(0, 1, 15, 16, 17, 32, 33, 100), seed=3):
+    """A hand-made (k, D) CSR whose row lengths cycle through `lengths`: empty rows, rows
+    shorter than k_srp_spmm's 16-wide load batch (tail only), exact multiples of it (no tail),
+    one past a multiple, and a dense row. Values +-1/sqrt(k) as the projection's."""
+    import scipy.sparse as sp
+
+    rng = np.random.default_rng(seed)
+    indptr, indices = [0], []
+    for r in range(k):
+        cols = np.sort(rng.choice(D, lengths[r % len(lengths)], replace=False))
+        indices.extend(cols.tolist())
+        indptr.append(len(indices))
+    data = (rng.choice([-1.0, 1.0], len(indices)) / np.sqrt(k)).astype(np.float32)
+    m = sp.csr_matrix((data, np.asarray(indices, np.int32), np.asarray(indptr, np.int32)), shape=(k, D))
+    assert sorted(set(np.diff(m.indptr).tolist())) == sorted(lengths)
+    return m
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B", [1, 64, 65])
+def test_gpu_projector_row_lengths_by_construction(dev, B):
+    # k = 70: the second block of 64 output rows holds 6; B = 65: a second batch block of one
+    comp = _cycled_csr()
+    X = np.random.default_rng(B).standard_normal((B, 100)).astype(np.float32)
+    got = S.SparseProjector(comp, dev)(torch.from_numpy(X).to(dev)).cpu().numpy()
+    ref = (comp.astype(np.float64) @ X.T.astype(np.float64)).T
+    scale = np.sqrt(np.abs(comp).astype(np.float64).power(2) @ (X.T.astype(np.float64) ** 2)).T + 1e-30
+    assert got.shape == (B, 70)
+    empty = np.diff(comp.indptr) == 0
+    assert empty.sum() == 9 and not got[:, empty].any()  # an empty row projects to exactly 0
+    err = float(np.max(np.abs(got - ref) / scale))
+    print(f"B={B}: max |err| / scale = {err:.3e} (tol 1e-5)")
+    assert err < 1e-5
+
+
 @pytest.mark.gpu
 def test_gpu_projector_strided_input(dev, tmp_path):
     t = S.get_srp_transformer(D=500, k=50, density=None, seed=1, cache_dir=str(tmp_path))

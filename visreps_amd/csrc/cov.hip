@@ -276,6 +276,13 @@ static void cov_geometry(int64_t n, int64_t p, int& T, int& ntile, int& S, int64
   S = (int)std::max<int64_t>(1, (n + kslice - 1) / kslice);
 }
 
+// The geometry of a launch, for the workspace size and for cov_launch alike. An empty row
+// set (n = 0: a rank with an empty shard) runs as one slice of zero stages, and its
+// workgroups still store their all-zero tiles, so it needs one slice of partials.
+static void cov_launch_geometry(int64_t n, int64_t p, int& T, int& ntile, int& S, int64_t& kslice) {
+  cov_geometry(std::max<int64_t>(n, 1), p, T, ntile, S, kslice);
+}
+
 }  // namespace vr
 
 using namespace vr;
@@ -313,10 +320,10 @@ int vr_mean_from_sum_f32(const float* sum, int64_t p, int64_t n, float* mean, vo
 }
 
 size_t vr_pca_cov_workspace(int64_t n, int64_t p) {
-  if (n <= 0 || p <= 0) return 256;
+  if (n < 0 || p <= 0) return 256;
   int T, ntile, S;
   int64_t kslice;
-  cov_geometry(n, p, T, ntile, S, kslice);
+  cov_launch_geometry(n, p, T, ntile, S, kslice);
   Carver c(nullptr);
   c.take<double>((size_t)S * ntile * CT * CT);
   return c.bytes();
@@ -331,7 +338,7 @@ static int cov_launch(bool trans, const float* X, int64_t n, int64_t p, int64_t 
   P.p = p;
   P.ldx = ldx;
   P.mean = mean;
-  cov_geometry(std::max<int64_t>(n, 1), p, P.T, P.ntile, P.S, P.kslice);
+  cov_launch_geometry(n, p, P.T, P.ntile, P.S, P.kslice);
   Carver c(ws);
   P.partial = c.take<double>((size_t)P.S * P.ntile * CT * CT);
   P.vec = (ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(X) & 15) == 0);

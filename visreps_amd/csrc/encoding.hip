@@ -13,6 +13,12 @@
 //                indices staged in LDS; five fp64 sums over the rows (coalesced row reads
 //                across the block's columns; Y and P stay L2/MALL resident across draws);
 //                per block the sum of its columns' r                       [HBM/L2-bound]
+//                The sums are of y - y0 and p - p0, with y0, p0 the column's values in the
+//                draw's first row, subtracted in fp64: r is shift-invariant, so the moments
+//                are taken where the one-pass variance sum/k - mean^2 does not cancel
+//                (error ~1e-14 at mean/std 1e4 instead of ~1e-8), and an exactly constant
+//                column has every term 0, hence variance exactly 0 and r = NaN whatever
+//                its value. Non-finite input gives a NaN variance and r = NaN.
 //  k_corr_fold   per draw, the block partials summed in fixed order / v -> score (fp64)
 #include "internal.h"
 
@@ -32,15 +38,21 @@ __global__ __launch_bounds__(CS_THREADS) void k_corr_cols(
   const bool on = c < v;
   const int32_t* my = idx ? idx + b * k : nullptr;
   double sy = 0, sp = 0, syy = 0, spp = 0, syp = 0;
+  double y0 = 0, p0 = 0;  // the column's pivots: its values in the draw's first row
   for (int64_t r0 = 0; r0 < k; r0 += CS_IDX) {
     const int m = (int)min<int64_t>(CS_IDX, k - r0);
     __syncthreads();
     for (int i = threadIdx.x; i < m; i += CS_THREADS) rows[i] = my ? my[r0 + i] : (int32_t)(r0 + i);
     __syncthreads();
     if (on) {
+      if (r0 == 0) {
+        const int64_t o = (int64_t)rows[0] * ld + c;
+        y0 = (double)Y[o];
+        p0 = (double)P[o];
+      }
       for (int i = 0; i < m; ++i) {
         const int64_t o = (int64_t)rows[i] * ld + c;
-        const double y = (double)Y[o], p = (double)P[o];
+        const double y = (double)Y[o] - y0, p = (double)P[o] - p0;
         sy += y;
         sp += p;
         syy += y * y;
@@ -55,7 +67,9 @@ __global__ __launch_bounds__(CS_THREADS) void k_corr_cols(
     const double my_ = sy / kk, mp = sp / kk;
     const double vy = syy / kk - my_ * my_, vp = spp / kk - mp * mp;
     const double cov = syp / kk - my_ * mp;
-    r = cov / sqrt((vy > 0 ? vy : 0.0) * (vp > 0 ? vp : 0.0));  // 0/0 -> NaN like zscore
+    // a constant column has every shifted term 0, so its variance is exactly 0; zero
+    // variance or non-finite input -> NaN, like zscore's 0/0
+    r = (vy > 0 && vp > 0) ? cov / sqrt(vy * vp) : __builtin_nan("");
     if (voxel_r) voxel_r[b * v + c] = r;
   }
   for (int o = 32; o > 0; o >>= 1) r += __shfl_down(r, o, 64);
