@@ -99,7 +99,10 @@ int vr_rdm_pearson_tiles_bf16(const uint16_t* X, int64_t n, int64_t d, int64_t l
  * encoding score's ridge regression: replaces the SVD inside himalaya 0.4.9's
  * RidgeCV(solver="svd") as called from visreps/analysis/encoding_score.py:47-62
  * (kernel form: X_val X_tr^T and X_tr X_tr^T are blocks of one Gram of the stacked rows).
- * Workspace: vr_rdm_pearson_workspace(n, d). G is exactly symmetric. */
+ * Always the exact-fp32 kernel, at any n^2 d (the split kernel's records hold centred rows).
+ * Workspace: vr_gram_workspace(n, d), which equals vr_rdm_pearson_workspace(n, d) wherever
+ * the RDM takes the fp32 kernel too. G is exactly symmetric. */
+size_t vr_gram_workspace(int64_t n, int64_t d);
 int vr_gram_f32(const float* X, int64_t n, int64_t d, int64_t ldx, float* G, int64_t ldg,
                 void* ws, size_t ws_bytes, void* stream);
 
@@ -346,6 +349,32 @@ size_t vr_bootstrap_pearson_workspace(int64_t n, int64_t n_sets);
 int vr_bootstrap_pearson_f32(const float* A, const float* B, int64_t n, int64_t ld,
                              const int32_t* idx, int64_t k, int64_t n_sets, int full_first,
                              double* scores, void* ws, size_t ws_bytes, void* stream);
+
+/* Linear CKA (analysis/metrics/_cka.py:10-22) of the sub-matrices K[idx][:, idx], L[idx][:, idx]
+ * (k rows idx [dev] int32 into the n x n kernel matrices, read in place; idx null with k == n:
+ * the whole matrices): two fp64 passes, row and grand means, then the sums of products of the
+ * double-centred entries. out [dev] 4 doubles: CKA, tr(KHLH), tr(KHKH), tr(LHLH) with
+ * H = I - 11^T / k (hsic is tr / (k - 1)^2). CKA is NaN for k < 2, non-finite input or a
+ * sub-matrix whose centred part is exactly zero (a constant one). K, L symmetric; idx must lie
+ * in [0, n): the kernels read unchecked. Bit-identical run to run. */
+size_t vr_cka_subset_workspace(int64_t k);
+int vr_cka_subset_f32(const float* K, const float* L, int64_t n, int64_t ld,
+                      const int32_t* idx, int64_t k, double* out,
+                      void* ws, size_t ws_bytes, void* stream);
+
+/* Bootstrapped linear CKA: the CKA of every subset as one masked fp64-MFMA GEMM over all
+ * subsets (csrc/cka_boot.hip). idx, k, n_sets, full_first, the scores layout, the error codes
+ * and the preconditions as vr_bootstrap_pearson_f32: distinct indices in [0, n) per row of
+ * idx, symmetric K and L ([dev] (n, n) row-major fp32, leading dimension ld). A subset scores
+ * NaN for k < 2, when some (i, j) with i and j in it (the diagonal included) is non-finite in K
+ * or L (and only then), or when a centred sub-matrix is zero; n < 2 gives all NaN without
+ * reading K or L. Scores are not clamped and are bit-identical run to run. Synchronises the
+ * stream once (the flags of the subsets that the two-pass kernels recompute). Workspace:
+ * vr_bootstrap_cka_workspace(n, n_sets) covers up to n_sets subsets plus the full set. */
+size_t vr_bootstrap_cka_workspace(int64_t n, int64_t n_sets);
+int vr_bootstrap_cka_f32(const float* K, const float* L, int64_t n, int64_t ld,
+                         const int32_t* idx, int64_t k, int64_t n_sets, int full_first,
+                         double* scores, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------
  * Phase-1 sparse random projection (extraction side).

@@ -64,6 +64,7 @@ _PROTOTYPES = {
         ctypes.c_int,
         [_vp, _c_i64, _c_i64, _c_i64, _vp, _c_i64, ctypes.c_float, _c_i64, _c_i64, _vp, _c_sz, _vp],
     ),
+    "vr_gram_workspace": (_c_sz, [_c_i64, _c_i64]),
     "vr_gram_f32": (
         ctypes.c_int,
         [_vp, _c_i64, _c_i64, _c_i64, _vp, _c_i64, _vp, _c_sz, _vp],
@@ -100,6 +101,16 @@ _PROTOTYPES = {
     ),
     "vr_bootstrap_pearson_workspace": (_c_sz, [_c_i64, _c_i64]),
     "vr_bootstrap_pearson_f32": (
+        ctypes.c_int,
+        [_vp, _vp, _c_i64, _c_i64, _vp, _c_i64, _c_i64, ctypes.c_int, _vp, _vp, _c_sz, _vp],
+    ),
+    "vr_cka_subset_workspace": (_c_sz, [_c_i64]),
+    "vr_cka_subset_f32": (
+        ctypes.c_int,
+        [_vp, _vp, _c_i64, _c_i64, _vp, _c_i64, _vp, _vp, _c_sz, _vp],
+    ),
+    "vr_bootstrap_cka_workspace": (_c_sz, [_c_i64, _c_i64]),
+    "vr_bootstrap_cka_f32": (
         ctypes.c_int,
         [_vp, _vp, _c_i64, _c_i64, _vp, _c_i64, _c_i64, ctypes.c_int, _vp, _vp, _c_sz, _vp],
     ),

@@ -79,7 +79,7 @@ def gram(x: torch.Tensor) -> torch.Tensor:
     if d == 0:
         return out.zero_()
     L = lib()
-    ws = workspace.get(dev, L.vr_rdm_pearson_workspace(n, d), "rdm")
+    ws = workspace.get(dev, L.vr_gram_workspace(n, d), "rdm")
     with torch.cuda.device(dev):
         check(L.vr_gram_f32(_ptr(x), n, d, x.stride(0), _ptr(out), n, _ptr(ws), ws.numel(),
                             stream_of(dev)), "vr_gram_f32")

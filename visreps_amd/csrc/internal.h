@@ -39,6 +39,22 @@ int radix_sort_kv(uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, uint32_t* 
 int pearson_two_pass(const float* A, const float* B, int64_t n_or_k, int64_t ld, const int32_t* idx,
                      double* out, double* part, double* mu, hipStream_t st);
 
+// ---- subset-indicator panels and shifts of the masked-GEMM engines (pearson_boot.hip) --
+// W: n_pad x s_pad bytes (both multiples of 64), W[i][off + s] = 1 iff stimulus i is in row s of
+// idx (n_sets x k), column 0 all ones over the rows < n when off == 1, 0 elsewhere. An index
+// outside [0, n) is skipped, never written.
+int pboot_build_w(uint8_t* W, const int32_t* idx, int64_t n, int64_t k, int64_t n_sets, int64_t n_pad,
+                  int64_t s_pad, int off, hipStream_t st);
+// shift[q] = float32((sum_a part[2 a + q]) / M) as a double, 0 if that is not finite (q = 0, 1)
+int pboot_shift(const double* part, int64_t n, double M, double* shift, hipStream_t st);
+
+// ---- two-pass fp64 CKA traces of two kernel matrices (cka_boot.hip) -----------------
+// idx == nullptr: the full n_or_k x n_or_k matrices; else K[idx][:, idx], L[idx][:, idx] read in
+// place. part: 5 n_or_k doubles, mu: 2 doubles. out: n_out doubles, 1 (the CKA) or 4 (CKA,
+// tr(KHLH), tr(KHKH), tr(LHLH)).
+int cka_two_pass(const float* K, const float* L, int64_t n_or_k, int64_t ld, const int32_t* idx,
+                 double* out, int n_out, double* part, double* mu, hipStream_t st);
+
 // ---- block-level helpers -----------------------------------------------------------
 // Exclusive scan across a block of BS threads (BS multiple of 64, <= 1024).
 // lds must hold BS/64 + 1 uint32. Returns this thread's exclusive prefix; total = sum.

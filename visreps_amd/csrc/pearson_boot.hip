@@ -15,7 +15,8 @@
 // means of the finite values rounded to float32, so x and y are exact in fp64.
 //
 // k_pboot_fill / k_pboot_scatter   W as bytes (n_pad x s_pad, both padded to 64 and zero
-//             there), plain byte / dword stores.
+//             there), plain byte / dword stores. pboot_build_w / pboot_shift launch them and
+//             k_pboot_shift for cka_boot.hip too.
 // k_pboot_shift_rows / k_pboot_shift   the two shifts (sums over finite values only, so a NaN
 //             in an RDM does not poison them).
 // k_pboot     a workgroup owns 64 rows i x 64 subsets and walks the columns j in panels of 16
@@ -136,6 +137,24 @@ __global__ __launch_bounds__(256) void k_pboot_shift(const double* __restrict__ 
     const float m = (float)((red[q][0] + red[q][1] + red[q][2] + red[q][3]) / M);
     shift[q] = pb_finite(m) ? (double)m : 0.0;
   }
+}
+
+int pboot_build_w(uint8_t* W, const int32_t* idx, int64_t n, int64_t k, int64_t n_sets, int64_t n_pad,
+                  int64_t s_pad, int off, hipStream_t st) {
+  const int64_t words = n_pad * (s_pad / 4);
+  k_pboot_fill<<<(unsigned)((words + 255) / 256), 256, 0, st>>>(reinterpret_cast<uint32_t*>(W), n, n_pad, s_pad, off);
+  VR_CHECK_LAUNCH();
+  if (n_sets * k > 0) {
+    k_pboot_scatter<<<(unsigned)((n_sets * k + 255) / 256), 256, 0, st>>>(W, idx, n, k, n_sets, s_pad, off);
+    VR_CHECK_LAUNCH();
+  }
+  return VR_OK;
+}
+
+int pboot_shift(const double* part, int64_t n, double M, double* shift, hipStream_t st) {
+  k_pboot_shift<<<1, 256, 0, st>>>(part, n, M, shift);
+  VR_CHECK_LAUNCH();
+  return VR_OK;
 }
 
 struct PbParams {
@@ -368,19 +387,11 @@ int vr_bootstrap_pearson_f32(const float* A, const float* B, int64_t n, int64_t 
     return VR_OK;
   }
   const PbLayout L = pb_layout(ws, n, total);
-  const int64_t words = L.n_pad * (L.s_pad / 4);
-  k_pboot_fill<<<(unsigned)((words + 255) / 256), 256, 0, st>>>(reinterpret_cast<uint32_t*>(L.W), n, L.n_pad,
-                                                               L.s_pad, off);
-  VR_CHECK_LAUNCH();
-  if (n_sets * k > 0) {
-    k_pboot_scatter<<<(unsigned)((n_sets * k + 255) / 256), 256, 0, st>>>(L.W, idx, n, k, n_sets, L.s_pad, off);
-    VR_CHECK_LAUNCH();
-  }
+  VR_TRY(pboot_build_w(L.W, idx, n, k, n_sets, L.n_pad, L.s_pad, off, st));
   const double m_full = (double)pairs_of(n), m_sub = (double)pairs_of(k);
   k_pboot_shift_rows<<<(unsigned)n, 256, 0, st>>>(A, B, n, ld, L.part);
   VR_CHECK_LAUNCH();
-  k_pboot_shift<<<1, 256, 0, st>>>(L.part, n, m_full, L.shift);
-  VR_CHECK_LAUNCH();
+  VR_TRY(pboot_shift(L.part, n, m_full, L.shift, st));
   PbParams P;
   P.A = A;
   P.B = B;

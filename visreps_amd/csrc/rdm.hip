@@ -1891,7 +1891,8 @@ static int rdm_launch(const void* Xv, int64_t n, int64_t d, int64_t ldx, float* 
   }
   hipStream_t st = as_stream(stream);
   GramParams P{};
-  const bool split3 = bf16 || pre.planes || gram_split(n, d);
+  // raw (vr_gram_f32) always takes the exact-fp32 kernel: the split kernel's records hold centred rows
+  const bool split3 = bf16 || pre.planes || (!raw && gram_split(n, d));
   float *mean, *stdv;
   uint16_t* planes;
   uint32_t* one_flag;
@@ -2094,6 +2095,11 @@ int vr_rdm_pearson_bf16(const uint16_t* X, int64_t n, int64_t d, int64_t ldx, fl
                                    ws_bytes, stream);
 }
 
+size_t vr_gram_workspace(int64_t n, int64_t d) {
+  if (n <= 0 || d <= 0) return 256;
+  return gram_ws(n, d, 0, gram_tiles(n), false, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
 int vr_gram_f32(const float* X, int64_t n, int64_t d, int64_t ldx, float* G, int64_t ldg,
                 void* ws, size_t ws_bytes, void* stream) {
   VR_REQUIRE(n >= 0 && d > 0 && ldx >= d && ldg >= n,
@@ -2102,8 +2108,7 @@ int vr_gram_f32(const float* X, int64_t n, int64_t d, int64_t ldx, float* G, int
   if (n == 0) return VR_OK;
   VR_REQUIRE(X && G, "vr_gram_f32: null pointer");
   VR_REQUIRE(n <= (1 << 20), "vr_gram_f32: n=%lld too large", (long long)n);
-  return rdm_launch(X, n, d, ldx, G, ldg, 0.f, 0, gram_tiles(n), ws, ws_bytes, stream,
-                    vr_rdm_pearson_workspace(n, d), true);
+  return rdm_launch(X, n, d, ldx, G, ldg, 0.f, 0, gram_tiles(n), ws, ws_bytes, stream, vr_gram_workspace(n, d), true);
 }
 
 
