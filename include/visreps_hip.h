@@ -255,7 +255,9 @@ int64_t vr_engine_est1_fallbacks(void);
 // totals. kernel: 0 k_rankB EST forms over bootstrap subsets, 1 k_rankB exact form, 2 k_rankA,
 // 3 k_join, 4 k_gram3p/k_gram3w (256^2 super-tiles), 5 k_gram3/k_gram (128^2 tiles),
 // 6 k_countA, 7 k_rankB EST 4 (the full-set pass: point estimates, phase-1 selections), 8 k_kwalk
-// (one Kendall stream walk of one pass), 9 k_cov (fp64 MFMA covariance / ridge Gram tiles).
+// (one Kendall stream walk of one pass), 9 k_cov (fp64 MFMA covariance / ridge Gram tiles),
+// 13 .. 16 the nearest-neighbour search of vr_knn2_f32: staging, k_knn_cand (units: FLOPs of the
+// tiles walked), merge + rerank, k_knn_exact_rows.
 // units: pairs walked (engine kernels) or tile FLOPs 2 d x tile elements (Gram kernels).
 // No reference counterpart (the reference has no native kernels).
 int vr_ktimer_enable(int on);
@@ -375,6 +377,28 @@ size_t vr_bootstrap_cka_workspace(int64_t n, int64_t n_sets);
 int vr_bootstrap_cka_f32(const float* K, const float* L, int64_t n, int64_t ld,
                          const int32_t* idx, int64_t k, int64_t n_sets, int full_first,
                          double* scores, void* ws, size_t ws_bytes, void* stream);
+
+/* Two nearest neighbours of every row, exact (csrc/knn.hip): the search behind the Facco Two-NN
+ * intrinsic dimensionality (analysis/compute_twoNN_ID.py:27-78). X [dev] (n, d) row-major fp32,
+ * leading dimension ldx >= d, finite, never written. r [dev] (n, 2) doubles: r1 <= r2, the two
+ * smallest Euclidean distances from the row to the other rows, each the square root of the fp64
+ * sum of the squared (exact) differences; nn [dev] (n, 2) int32 their rows (nullable), ties to
+ * the lower index. An fp32-MFMA candidate pass on a centred scratch copy keeps 4 candidates and
+ * a cut per row and never forms the n x n matrix; a row whose error bound cannot separate its
+ * second distance from the cut is scanned against all rows in fp64. Bit-identical run to run.
+ * n < 3 writes NaN distances and -1 indices; n = 0 writes nothing. VR_EINVAL for n < 0,
+ * n > 2^20, d < 1, ldx < d or a null X or r; VR_EWORKSPACE for ws_bytes below
+ * vr_knn2_workspace(n, d) (linear in n, non-decreasing in n and d). Synchronises the stream once
+ * (the number of rows to scan). vr_knn2_last_fallback_rows: rows of the last call on this
+ * thread that took the exact scan. */
+size_t vr_knn2_workspace(int64_t n, int64_t d);
+int vr_knn2_f32(const float* X, int64_t n, int64_t d, int64_t ldx, double* r, int32_t* nn,
+                void* ws, size_t ws_bytes, void* stream);
+int64_t vr_knn2_last_fallback_rows(void);
+/* Two-NN estimate from r [dev] (n, 2): out [dev] 2 doubles, [1 / mean log(r2 / r1), kept] over
+ * the rows with r1 > 0 (kept), added in a fixed order; NaN when no row is kept, inf when the
+ * mean is zero. */
+int vr_twonn_id_f64(const double* r, int64_t n, double* out, void* stream);
 
 /* ------------------------------------------------------------------------------
  * Phase-1 sparse random projection (extraction side).

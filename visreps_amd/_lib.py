@@ -114,6 +114,10 @@ _PROTOTYPES = {
         ctypes.c_int,
         [_vp, _vp, _c_i64, _c_i64, _vp, _c_i64, _c_i64, ctypes.c_int, _vp, _vp, _c_sz, _vp],
     ),
+    "vr_knn2_workspace": (_c_sz, [_c_i64, _c_i64]),
+    "vr_knn2_f32": (ctypes.c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _c_sz, _vp]),
+    "vr_knn2_last_fallback_rows": (_c_i64, []),
+    "vr_twonn_id_f64": (ctypes.c_int, [_vp, _c_i64, _vp, _vp]),
     "vr_bootstrap_workspace": (_c_sz, [_c_i64]),
     "vr_bootstrap_spearman_plans": (
         ctypes.c_int,
@@ -331,6 +335,8 @@ KTIMER_KERNELS = {"k_rankB_est": 0, "k_rankB_exact": 1, "k_rankA": 2, "k_join": 
                   "k_gram_wide": 4, "k_gram_tile": 5, "k_countA": 6, "k_rankB_full": 7,
                   "k_kwalk": 8, "k_cov": 9, "k_join4": 10,
                   "k_full_corr": 11, "k_rankB_grid": 12}
+# the nearest-neighbour search (csrc/knn.hip): staging, candidate pass, merge + rerank, exact scan
+KTIMER_KNN = {"knn_stage": 13, "k_knn_cand": 14, "knn_rerank": 15, "k_knn_exact_rows": 16}
 
 
 def ktimer_enable(on: bool = True) -> None:
@@ -343,7 +349,8 @@ def ktimer_read(kernel: str) -> tuple[float, int, float]:
     """(total ms, launches, units) of one hot kernel since ktimer_enable; units are pairs
     walked (engine kernels) or tile FLOPs (Gram kernels)."""
     ms, n, u = ctypes.c_double(), ctypes.c_int64(), ctypes.c_double()
-    check(lib().vr_ktimer_read(KTIMER_KERNELS[kernel], ctypes.byref(ms), ctypes.byref(n), ctypes.byref(u)),
+    kid = KTIMER_KERNELS[kernel] if kernel in KTIMER_KERNELS else KTIMER_KNN[kernel]
+    check(lib().vr_ktimer_read(kid, ctypes.byref(ms), ctypes.byref(n), ctypes.byref(u)),
           "vr_ktimer_read")
     return ms.value, n.value, u.value
 

@@ -125,7 +125,11 @@ enum KtKernel : int {
   KT_JOIN4 = 10,      // k_join4: shared join of one B plan to up to 4 A plans (units = algorithmic bytes)
   KT_FULL_CORR = 11,  // k_full_corr: lane 0's shift sums of an EST 4 pass, per unit (4 B / pair streamed)
   KT_RANKB_GRID = 12,  // k_rankB_grid: one B plan x up to 4 regions, EST 3 (units: pairs x regions)
-  KT_N = 13
+  KT_KNN_STAGE = 13,  // knn.hip: column means, centred copy, norms (units: bytes of X read)
+  KT_KNN_CAND = 14,   // k_knn_cand (units: fp32 FLOPs of the tiles walked)
+  KT_KNN_RERANK = 15, // k_knn_merge + k_knn_rerank (units: candidate pairs)
+  KT_KNN_EXACT = 16,  // k_knn_exact_rows (units: pairs scanned)
+  KT_N = 17
 };
 bool ktimer_on();
 struct KtScope {
