@@ -590,6 +590,38 @@ size_t vr_gram64_workspace(int64_t n, int64_t p, int rows);
 int vr_gram64_f32(const float* X, int64_t n, int64_t p, int64_t ldx, int rows, double* G, int64_t ldg,
                   void* ws, size_t ws_bytes, void* stream);
 
+/* Centred fp64 Grams about an fp64 mean (the eigenspectrum's covariance on its smaller side,
+ * analysis/compute_eigenspectra.py): the tiles of vr_pca_cov_f64 / vr_gram64_f32 with
+ * (double)x - mean formed while staging. vr_col_mean_f64: mean [dev] p doubles, the fp64 sum of
+ * each column in row order / n (n >= 1; the column-sum kernels of csrc/knn.hip, no workspace).
+ * vr_centred_gram64_f32: rows = 0: G = (X - mean)^T (X - mean) / denom (p x p); rows = 1:
+ * G = (X - mean)(X - mean)^T / denom (n x n), the mean indexed along the contraction. mean [dev]
+ * p doubles either way. G [dev] fp64, leading dimension ldg, exactly symmetric. n >= 1, p >= 1.
+ * VR_EWORKSPACE below vr_centred_gram64_workspace(n, p, rows). */
+int vr_col_mean_f64(const float* X, int64_t n, int64_t p, int64_t ldx, double* mean, void* stream);
+size_t vr_centred_gram64_workspace(int64_t n, int64_t p, int rows);
+int vr_centred_gram64_f32(const float* X, int64_t n, int64_t p, int64_t ldx, const double* mean,
+                          int rows, double denom, double* G, int64_t ldg, void* ws,
+                          size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------
+ * Eigenvalues of a dense symmetric fp64 matrix, no vectors (csrc/eigvals.hip): unblocked
+ * Householder tridiagonalisation, then Sturm-sequence bisection, one lane per eigenvalue.
+ * Replaces the eigenvalue half of sklearn PCA(svd_solver="full") in
+ * visreps/analysis/compute_eigenspectra.py:11-37 and np.linalg.eigvalsh in
+ * experiments/representation_analysis/dimensionality/metrics.py:12-33.
+ * A [dev] m x m, symmetric with both triangles filled, leading dimension lda >= m; its
+ * contents are destroyed. w [dev] m doubles, ascending. m = 0 writes nothing; m = 1 and m = 2
+ * skip the reduction. A non-finite entry anywhere in A gives all-NaN w. Backward stable:
+ * |w - lambda| <= c m eps max|lambda|. Bit-identical run to run (fixed-order reductions, no
+ * float atomics); no host synchronisation, every launch on the caller's stream; every loop's
+ * trip count depends on m alone. VR_EINVAL for m < 0, m > 65536, lda < m or a null A or w;
+ * VR_EWORKSPACE for ws_bytes below vr_eigvalsh_workspace(m) (O(m), non-decreasing in m).
+ * -------------------------------------------------------------------------- */
+size_t vr_eigvalsh_workspace(int64_t m);
+int vr_eigvalsh_f64(double* A, int64_t m, int64_t lda, double* w, void* ws, size_t ws_bytes,
+                    void* stream);
+
 /* ------------------------------------------------------------------------------
  * Host: legacy numpy RandomState (MT19937) index streams, bit-exact.
  * Replaces np.random.RandomState(seed) + .choice(n, k, replace=False) / .permutation(n)

@@ -186,6 +186,14 @@ _PROTOTYPES = {
     ),
     "vr_gram64_workspace": (_c_sz, [_c_i64, _c_i64, ctypes.c_int]),
     "vr_gram64_f32": (ctypes.c_int, [_vp, _c_i64, _c_i64, _c_i64, ctypes.c_int, _vp, _c_i64, _vp, _c_sz, _vp]),
+    "vr_col_mean_f64": (ctypes.c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _vp]),
+    "vr_centred_gram64_workspace": (_c_sz, [_c_i64, _c_i64, ctypes.c_int]),
+    "vr_centred_gram64_f32": (
+        ctypes.c_int,
+        [_vp, _c_i64, _c_i64, _c_i64, _vp, ctypes.c_int, ctypes.c_double, _vp, _c_i64, _vp, _c_sz, _vp],
+    ),
+    "vr_eigvalsh_workspace": (_c_sz, [_c_i64]),
+    "vr_eigvalsh_f64": (ctypes.c_int, [_vp, _c_i64, _c_i64, _vp, _vp, _c_sz, _vp]),
     "vr_spearman_full_workspace": (_c_sz, [_c_i64]),
     "vr_spearman_full_sort_workspace": (_c_sz, [_c_i64]),
     "vr_spearman_full_last_form": (ctypes.c_int, []),
@@ -338,6 +346,9 @@ KTIMER_KERNELS = {"k_rankB_est": 0, "k_rankB_exact": 1, "k_rankA": 2, "k_join": 
 # the nearest-neighbour search (csrc/knn.hip): staging, candidate pass, merge + rerank, exact scan
 KTIMER_KNN = {"knn_stage": 13, "k_knn_cand": 14, "knn_rerank": 15, "k_knn_exact_rows": 16}
 
+# the symmetric eigensolver (csrc/eigvals.hip): all of stage A of a call, bounds + bisection
+KTIMER_EIG = {"eig_tridiag": 17, "eig_bisect": 18}
+
 
 def ktimer_enable(on: bool = True) -> None:
     """Start (clearing the totals) or stop the library's per-launch HIP-event timing of the
@@ -349,7 +360,8 @@ def ktimer_read(kernel: str) -> tuple[float, int, float]:
     """(total ms, launches, units) of one hot kernel since ktimer_enable; units are pairs
     walked (engine kernels) or tile FLOPs (Gram kernels)."""
     ms, n, u = ctypes.c_double(), ctypes.c_int64(), ctypes.c_double()
-    kid = KTIMER_KERNELS[kernel] if kernel in KTIMER_KERNELS else KTIMER_KNN[kernel]
+    kid = (KTIMER_KERNELS[kernel] if kernel in KTIMER_KERNELS else
+           KTIMER_KNN[kernel] if kernel in KTIMER_KNN else KTIMER_EIG[kernel])
     check(lib().vr_ktimer_read(kid, ctypes.byref(ms), ctypes.byref(n), ctypes.byref(u)),
           "vr_ktimer_read")
     return ms.value, n.value, u.value

@@ -17,6 +17,9 @@
 //             writes its fp64 partial tile and k_cov_reduce adds the slices in fixed order,
 //             divides by the denominator and writes each entry and its mirror (the result
 //             is exactly symmetric, like the reference's batch.T @ batch).
+//             k_cov<.., true> centres about an fp64 mean instead (the eigenspectrum's Gram,
+//             vr_centred_gram64_f32): per column as above, or, read transposed, per contraction
+//             index for the n x n form.
 // Roofline: fp64 MFMA, algorithmic FLOPs = n p (p + 1) (the unique entries i <= j).
 #include "internal.h"
 
@@ -90,6 +93,7 @@ struct CovParams {
   int S;            // row slices
   int64_t kslice;   // rows per slice (multiple of CK)
   bool vec;         // 16-B aligned rows: float4 panel loads
+  const double* mean64;  // k_cov<.., true>: the fp64 mean (length p, or n of the contraction when TRANS)
 };
 
 // TRANS (the kernel-form ridge Gram X X^T of a row-major (p, n) X): the contraction runs
@@ -114,6 +118,18 @@ __device__ inline void cov_store_t(double* lds, const cf32x4 v) {
   const int c = threadIdx.x >> 2, kq = (threadIdx.x & 3) * 4;
 #pragma unroll
   for (int e = 0; e < 4; ++e) lds[(kq + e) * CLD + c] = (double)v[e];  // out-of-range entries are 0
+}
+
+// ... centred about the fp64 mean of the contraction index (the rows-side centred Gram)
+__device__ inline void cov_store_t64(const CovParams& P, double* lds, const cf32x4 v, int64_t col0, int64_t k,
+                                     int64_t k1) {
+  const int c = threadIdx.x >> 2, kq = (threadIdx.x & 3) * 4;
+  const bool cin = col0 + c < P.p;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int64_t r = k + kq + e;
+    lds[(kq + e) * CLD + c] = (cin && r < k1) ? (double)v[e] - P.mean64[r] : 0.0;
+  }
 }
 
 // tile t of the upper triangle (row-major: (0,0), (0,1), .., (0,T-1), (1,1), ..)
@@ -151,7 +167,8 @@ __device__ inline void cov_store(double* lds, const cf32x4 v, const double m[4],
   for (int e = 0; e < 4; ++e) dst[e] = in ? (double)v[e] - m[e] : 0.0;  // padded rows add exact zeros
 }
 
-template <bool TRANS>
+// M64: centre about P.mean64 (fp64) instead of P.mean (fp32)
+template <bool TRANS, bool M64 = false>
 __global__ __launch_bounds__(C_THREADS, 2) void k_cov(CovParams P) {
   __shared__ __attribute__((aligned(16))) double lds[2][2][C_STAGE];  // [buf][A/B]
   const int id = (int)xcd_remap(blockIdx.x, gridDim.x);
@@ -171,8 +188,13 @@ __global__ __launch_bounds__(C_THREADS, 2) void k_cov(CovParams P) {
     const int c = (threadIdx.x & 15) * 4;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      mA[e] = (P.mean && ci + c + e < P.p) ? (double)P.mean[ci + c + e] : 0.0;
-      mB[e] = (P.mean && cj + c + e < P.p) ? (double)P.mean[cj + c + e] : 0.0;
+      if constexpr (M64) {
+        mA[e] = (!TRANS && ci + c + e < P.p) ? P.mean64[ci + c + e] : 0.0;
+        mB[e] = (!TRANS && cj + c + e < P.p) ? P.mean64[cj + c + e] : 0.0;
+      } else {
+        mA[e] = (P.mean && ci + c + e < P.p) ? (double)P.mean[ci + c + e] : 0.0;
+        mB[e] = (P.mean && cj + c + e < P.p) ? (double)P.mean[cj + c + e] : 0.0;
+      }
     }
   }
   f64x4 acc[2][2];
@@ -183,7 +205,9 @@ __global__ __launch_bounds__(C_THREADS, 2) void k_cov(CovParams P) {
 
   auto load = [&](int64_t col0, int64_t k) { return TRANS ? cov_load_t(P, col0, k, k1) : cov_load(P, col0, k, k1); };
   auto store = [&](double* dst, const cf32x4 v, const double* m, int64_t k) {
-    if constexpr (TRANS)
+    if constexpr (TRANS && M64)
+      cov_store_t64(P, dst, v, m == mA ? ci : cj, k, k1);  // m names the panel: mA goes with ci
+    else if constexpr (TRANS)
       cov_store_t(dst, v);
     else
       cov_store(dst, v, m, k, k1);
@@ -331,8 +355,10 @@ size_t vr_pca_cov_workspace(int64_t n, int64_t p) {
 
 // (n = contraction length, p = output order) -> k_cov + k_cov_reduce
 static int cov_launch(bool trans, const float* X, int64_t n, int64_t p, int64_t ldx, const float* mean,
-                      double denom, double* cov, int64_t ldc, void* ws, hipStream_t st) {
+                      double denom, double* cov, int64_t ldc, void* ws, hipStream_t st,
+                      const double* mean64 = nullptr) {
   CovParams P;
+  P.mean64 = mean64;
   P.X = X;
   P.n = n;
   P.p = p;
@@ -344,7 +370,11 @@ static int cov_launch(bool trans, const float* X, int64_t n, int64_t p, int64_t 
   P.vec = (ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(X) & 15) == 0);
   {
     KtScope kt(KT_COV, (double)n * (double)p * (double)(p + 1), st);  // algorithmic FLOPs
-    if (trans)
+    if (mean64 != nullptr && trans)
+      k_cov<true, true><<<(unsigned)(P.ntile * P.S), C_THREADS, 0, st>>>(P);
+    else if (mean64 != nullptr)
+      k_cov<false, true><<<(unsigned)(P.ntile * P.S), C_THREADS, 0, st>>>(P);
+    else if (trans)
       k_cov<true><<<(unsigned)(P.ntile * P.S), C_THREADS, 0, st>>>(P);
     else
       k_cov<false><<<(unsigned)(P.ntile * P.S), C_THREADS, 0, st>>>(P);
@@ -383,6 +413,33 @@ int vr_gram64_f32(const float* X, int64_t n, int64_t p, int64_t ldx, int rows, d
   }
   VR_REQUIRE(p >= 1, "vr_gram64_f32: columns Gram of zero-width X");
   return cov_launch(false, X, n, p, ldx, nullptr, 1.0, G, ldg, ws, as_stream(stream));
+}
+
+int vr_col_mean_f64(const float* X, int64_t n, int64_t p, int64_t ldx, double* mean, void* stream) {
+  clear_error();
+  VR_REQUIRE(n >= 1 && p >= 0 && ldx >= p, "vr_col_mean_f64: bad shape n=%lld p=%lld ldx=%lld", (long long)n,
+             (long long)p, (long long)ldx);
+  if (p == 0) return VR_OK;
+  VR_REQUIRE(X != nullptr && mean != nullptr, "vr_col_mean_f64: null pointer");
+  return knn_col_mean_f64(X, n, p, ldx, mean, as_stream(stream));
+}
+
+size_t vr_centred_gram64_workspace(int64_t n, int64_t p, int rows) { return vr_gram64_workspace(n, p, rows); }
+
+int vr_centred_gram64_f32(const float* X, int64_t n, int64_t p, int64_t ldx, const double* mean, int rows,
+                          double denom, double* G, int64_t ldg, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  VR_REQUIRE(n >= 1 && p >= 1 && ldx >= p, "vr_centred_gram64_f32: bad shape n=%lld p=%lld ldx=%lld",
+             (long long)n, (long long)p, (long long)ldx);
+  VR_REQUIRE(ldg >= (rows ? n : p), "vr_centred_gram64_f32: ldg %lld too small", (long long)ldg);
+  VR_REQUIRE(X != nullptr && mean != nullptr && G != nullptr, "vr_centred_gram64_f32: null pointer");
+  if (ws == nullptr || ws_bytes < vr_centred_gram64_workspace(n, p, rows)) {
+    set_error("vr_centred_gram64_f32: workspace too small");
+    return VR_EWORKSPACE;
+  }
+  if (rows)  // (X - mean)(X - mean)^T: contraction over the p columns, the mean indexed along it
+    return cov_launch(true, X, p, n, ldx, nullptr, denom, G, ldg, ws, as_stream(stream), mean);
+  return cov_launch(false, X, n, p, ldx, nullptr, denom, G, ldg, ws, as_stream(stream), mean);
 }
 
 }  // extern "C"

@@ -55,6 +55,10 @@ int pboot_shift(const double* part, int64_t n, double M, double* shift, hipStrea
 int cka_two_pass(const float* K, const float* L, int64_t n_or_k, int64_t ld, const int32_t* idx,
                  double* out, int n_out, double* part, double* mu, hipStream_t st);
 
+// ---- fp64 column means of fp32 rows (knn.hip: k_knn_colsum / k_knn_colmean) ----------
+// mean[c] = (sum over rows, in row order, of (double)X[r][c]) / n for c < d. No workspace.
+int knn_col_mean_f64(const float* X, int64_t n, int64_t d, int64_t ldx, double* mean, hipStream_t st);
+
 // ---- block-level helpers -----------------------------------------------------------
 // Exclusive scan across a block of BS threads (BS multiple of 64, <= 1024).
 // lds must hold BS/64 + 1 uint32. Returns this thread's exclusive prefix; total = sum.
@@ -129,7 +133,9 @@ enum KtKernel : int {
   KT_KNN_CAND = 14,   // k_knn_cand (units: fp32 FLOPs of the tiles walked)
   KT_KNN_RERANK = 15, // k_knn_merge + k_knn_rerank (units: candidate pairs)
   KT_KNN_EXACT = 16,  // k_knn_exact_rows (units: pairs scanned)
-  KT_N = 17
+  KT_EIG_TRIDIAG = 17,  // eigvals.hip stage A: all Householder steps of one call (units: bytes of A22 moved)
+  KT_EIG_BISECT = 18,   // eigvals.hip stage B: bounds + bisection (units: Sturm terms)
+  KT_N = 19
 };
 bool ktimer_on();
 struct KtScope {

@@ -83,17 +83,27 @@ __global__ __launch_bounds__(256) void k_knn_colsum(const float* __restrict__ X,
   if (c >= d) return;
   const int64_t r0 = (int64_t)blockIdx.y * rows_per, r1 = min(n, r0 + rows_per);
   double s = 0.0;
-  for (int64_t r = r0; r < r1; ++r) s += (double)X[r * ldx + c];
+  int64_t r = r0;
+  for (; r + 16 <= r1; r += 16) {  // 16 loads in flight; the additions keep the row order
+    float x[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) x[u] = X[(r + u) * ldx + c];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) s += (double)x[u];
+  }
+  for (; r < r1; ++r) s += (double)X[r * ldx + c];
   part[(int64_t)blockIdx.y * d + c] = s;
 }
 
-__global__ __launch_bounds__(256) void k_knn_colmean(const double* __restrict__ part, int64_t n, int64_t d,
-                                                     int chunks, float* __restrict__ mu) {
+// T = float for the search's staging, double for knn_col_mean_f64 (there mu may be part: one chunk,
+// each thread reads its own entry before it writes it)
+template <class T>
+__global__ __launch_bounds__(256) void k_knn_colmean(const double* part, int64_t n, int64_t d, int chunks, T* mu) {
   const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (c >= d) return;
   double s = 0.0;
   for (int b = 0; b < chunks; ++b) s += part[(int64_t)b * d + c];
-  mu[c] = (float)(s / (double)n);
+  mu[c] = (T)(s / (double)n);
 }
 
 // block sum of 256 threads: wave shuffle tree, then the four waves in order
@@ -560,6 +570,16 @@ static int exact_scan(const float* X, int64_t n, int64_t d, int64_t ldx, const i
   return VR_OK;
 }
 
+// fp64 column means with no workspace: one chunk of rows, summed in row order into mean itself
+int knn_col_mean_f64(const float* X, int64_t n, int64_t d, int64_t ldx, double* mean, hipStream_t st) {
+  const unsigned grid = (unsigned)((d + 255) / 256);
+  k_knn_colsum<<<dim3(grid, 1), 256, 0, st>>>(X, n, d, ldx, n, mean);
+  VR_CHECK_LAUNCH();
+  k_knn_colmean<double><<<grid, 256, 0, st>>>(mean, n, d, 1, mean);
+  VR_CHECK_LAUNCH();
+  return VR_OK;
+}
+
 }  // namespace vr
 
 using namespace vr;
@@ -603,7 +623,7 @@ int vr_knn2_f32(const float* X, int64_t n, int64_t d, int64_t ldx, double* r, in
     k_knn_colsum<<<dim3((unsigned)((d + 255) / 256), (unsigned)Y.chunks), 256, 0, st>>>(X, n, d, ldx, rows_per,
                                                                                       Y.colpart);
     VR_CHECK_LAUNCH();
-    k_knn_colmean<<<(unsigned)((d + 255) / 256), 256, 0, st>>>(Y.colpart, n, d, Y.chunks, Y.mu);
+    k_knn_colmean<float><<<(unsigned)((d + 255) / 256), 256, 0, st>>>(Y.colpart, n, d, Y.chunks, Y.mu);
     VR_CHECK_LAUNCH();
     k_knn_stage<<<(unsigned)Y.n_pad, 256, 0, st>>>(X, n, d, ldx, Y.mu, Y.Y, Y.d_pad, Y.a64, Y.a32);
     VR_CHECK_LAUNCH();
