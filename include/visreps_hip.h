@@ -257,7 +257,9 @@ int64_t vr_engine_est1_fallbacks(void);
 // 6 k_countA, 7 k_rankB EST 4 (the full-set pass: point estimates, phase-1 selections), 8 k_kwalk
 // (one Kendall stream walk of one pass), 9 k_cov (fp64 MFMA covariance / ridge Gram tiles),
 // 13 .. 16 the nearest-neighbour search of vr_knn2_f32: staging, k_knn_cand (units: FLOPs of the
-// tiles walked), merge + rerank, k_knn_exact_rows.
+// tiles walked), merge + rerank, k_knn_exact_rows; 17 .. 20 the symmetric eigensolver: stage A
+// (units: bytes of A22 moved), bounds + bisection, and for vr_eigh_top_f64 the inverse iterations
+// (stage C) and the back-transformation (stage D).
 // units: pairs walked (engine kernels) or tile FLOPs 2 d x tile elements (Gram kernels).
 // No reference counterpart (the reference has no native kernels).
 int vr_ktimer_enable(int on);
@@ -621,6 +623,31 @@ int vr_centred_gram64_f32(const float* X, int64_t n, int64_t p, int64_t ldx, con
 size_t vr_eigvalsh_workspace(int64_t m);
 int vr_eigvalsh_f64(double* A, int64_t m, int64_t lda, double* w, void* ws, size_t ws_bytes,
                     void* stream);
+
+/* The k algebraically largest eigenpairs of the same kind of matrix, 0 <= k <= m <= 65536, on the
+ * same solver (csrc/eigvals.hip); replaces the full torch.linalg.eigh of
+ * analysis/reconstruct_from_pcs.py and scripts/coarsegrain/compute_eigenvectors.py where a few
+ * leading vectors are kept. A as above, destroyed. w [dev] k doubles, descending: w[j] is bit for
+ * bit vr_eigvalsh_f64's w[m - 1 - j]. V [dev] k x m row-major, leading dimension ldv >= m: row j
+ * is the unit eigenvector of w[j], its largest-magnitude entry positive (the lowest index on a
+ * tie); entries past column m of a row are not written.
+ *   stage A  the tridiagonalisation of vr_eigvalsh_f64, each Householder vector stored back over
+ *            the row it annihilated and its tau in the workspace
+ *   stage B  bisection of the top k indices only
+ *   stage C  a fixed number of inverse iterations on the tridiagonal, one lane per vector
+ *            (partial pivoting, small pivots replaced, max-abs scaling); coincident eigenvalues
+ *            separated by 4 eps span; after each iteration vectors whose eigenvalues chain
+ *            within 1e-3 span are orthogonalised in order (modified Gram-Schmidt, two passes)
+ *   stage D  V <- Q V, one workgroup per vector applying the m - 2 reflectors in turn
+ * Residual ||A v - w v||_2 and orthogonality max|V V^T - I| are of order m eps ||A||_2 and m eps.
+ * k = 0 or m = 0 writes nothing; m = 1 gives V = [[1]]. A non-finite entry of A gives NaN in all
+ * of w and V; a zero matrix gives w = 0 exactly and k orthonormal vectors. Bit-identical run to
+ * run; no host synchronisation; every loop's trip count depends on m and k alone. VR_EINVAL for
+ * m < 0, m > 65536, k < 0, k > m, lda < m, ldv < m or a null A, w or V that would be used;
+ * VR_EWORKSPACE for ws_bytes below vr_eigh_top_workspace(m, k) (O(m k), non-decreasing in both). */
+size_t vr_eigh_top_workspace(int64_t m, int64_t k);
+int vr_eigh_top_f64(double* A, int64_t m, int64_t lda, int64_t k, double* w, double* V, int64_t ldv,
+                    void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------
  * Host: legacy numpy RandomState (MT19937) index streams, bit-exact.

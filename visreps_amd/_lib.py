@@ -194,6 +194,8 @@ _PROTOTYPES = {
     ),
     "vr_eigvalsh_workspace": (_c_sz, [_c_i64]),
     "vr_eigvalsh_f64": (ctypes.c_int, [_vp, _c_i64, _c_i64, _vp, _vp, _c_sz, _vp]),
+    "vr_eigh_top_workspace": (_c_sz, [_c_i64, _c_i64]),
+    "vr_eigh_top_f64": (ctypes.c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_sz, _vp]),
     "vr_spearman_full_workspace": (_c_sz, [_c_i64]),
     "vr_spearman_full_sort_workspace": (_c_sz, [_c_i64]),
     "vr_spearman_full_last_form": (ctypes.c_int, []),
@@ -346,8 +348,9 @@ KTIMER_KERNELS = {"k_rankB_est": 0, "k_rankB_exact": 1, "k_rankA": 2, "k_join": 
 # the nearest-neighbour search (csrc/knn.hip): staging, candidate pass, merge + rerank, exact scan
 KTIMER_KNN = {"knn_stage": 13, "k_knn_cand": 14, "knn_rerank": 15, "k_knn_exact_rows": 16}
 
-# the symmetric eigensolver (csrc/eigvals.hip): all of stage A of a call, bounds + bisection
-KTIMER_EIG = {"eig_tridiag": 17, "eig_bisect": 18}
+# the symmetric eigensolver (csrc/eigvals.hip): all of stage A of a call, bounds + bisection, and
+# for vr_eigh_top_f64 the inverse iterations (stage C) and the back-transformation (stage D)
+KTIMER_EIG = {"eig_tridiag": 17, "eig_bisect": 18, "eig_invit": 19, "eig_back": 20}
 
 
 def ktimer_enable(on: bool = True) -> None:

@@ -3,6 +3,7 @@ spectrum functions of experiments/representation_analysis/dimensionality/metrics
 covariance on the fp64 MFMA and the eigenvalues from a hand-written symmetric eigensolver.
 
   eigvalsh                    ascending eigenvalues of a symmetric fp64 matrix (vr_eigvalsh_f64)
+  eigh_top                    the k largest eigenpairs of one, descending, signs fixed (vr_eigh_top_f64)
   centred_gram                (X - mean)^T (X - mean) / denom or its rows form, fp64, about the fp64 mean
   eigenspectrum               eigenvalues of the covariance about the column mean, descending, clipped at 0
   participation_ratio, cumulative_variance, n_components_for_variance   summaries of that spectrum
@@ -27,7 +28,7 @@ import torch
 from .._lib import check, lib, stream_of, workspace
 from .rsa import _device_for, _ptr
 
-__all__ = ["MAX_ORDER", "eigvalsh", "centred_gram", "eigenspectrum", "participation_ratio",
+__all__ = ["MAX_ORDER", "eigvalsh", "eigh_top", "centred_gram", "eigenspectrum", "participation_ratio",
            "cumulative_variance", "n_components_for_variance", "analyze_layer_pca", "process_file", "main"]
 
 MAX_ORDER = 65536  # largest matrix order of vr_eigvalsh_f64
@@ -68,6 +69,44 @@ def _eigvalsh_inplace(a: torch.Tensor) -> torch.Tensor:
     with torch.cuda.device(dev):
         check(L.vr_eigvalsh_f64(_ptr(a), m, m, _ptr(w), _ptr(ws), ws.numel(), stream_of(dev)), "vr_eigvalsh_f64")
     return w
+
+
+def eigh_top(A: torch.Tensor, k: int):
+    """(w, V): the k algebraically largest eigenvalues of the symmetric float64 matrix A, descending,
+    and their unit eigenvectors in the columns of V (m, k), the transposed view of the solver's
+    k x m buffer. w[j] is bit for bit eigvalsh(A)[m - 1 - j]; every vector's largest-magnitude
+    entry is positive (the lowest index on a tie), so the result does not depend on a library
+    version. Conventions as eigvalsh: A is not written, a CPU tensor goes to the current device and
+    the results come back, a non-finite entry gives all NaN."""
+    if not isinstance(A, torch.Tensor):
+        A = torch.as_tensor(np.asarray(A))
+    if A.ndim != 2 or A.size(0) != A.size(1):
+        raise ValueError(f"A must be square: got shape {tuple(A.shape)}")
+    if A.dtype != torch.float64:
+        raise TypeError(f"A must be float64: got {A.dtype}")
+    m, k = int(A.size(0)), int(k)
+    _check_order(m)
+    if not 0 <= k <= m:
+        raise ValueError(f"k={k} must be between 0 and the order {m}")
+    dev = _device_for(A)
+    a = A.to(dev).clone(memory_format=torch.contiguous_format)
+    w, V = _eigh_top_inplace(a, k)
+    return (w, V) if A.is_cuda else (w.cpu(), V.cpu())
+
+
+def _eigh_top_inplace(a: torch.Tensor, k: int):
+    """vr_eigh_top_f64 on the contiguous device matrix a, which it destroys."""
+    dev, m = a.device, int(a.size(0))
+    w = torch.empty(k, dtype=torch.float64, device=dev)
+    Vt = torch.empty((k, m), dtype=torch.float64, device=dev)
+    if m == 0 or k == 0:
+        return w, Vt.T
+    L = lib()
+    ws = workspace.get(dev, L.vr_eigh_top_workspace(m, k), "eigh_top")
+    with torch.cuda.device(dev):
+        check(L.vr_eigh_top_f64(_ptr(a), m, m, k, _ptr(w), _ptr(Vt), m, _ptr(ws), ws.numel(), stream_of(dev)),
+              "vr_eigh_top_f64")
+    return w, Vt.T
 
 
 def _rows_f32(X) -> torch.Tensor:

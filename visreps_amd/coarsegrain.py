@@ -14,7 +14,10 @@ Device path (csrc/cov.hip):
               its 10000-row batches with BLAS dgemm; here the rows are summed in fixed
               row slices, so entries agree to fp64 rounding (~1e-15 relative), and
               ``batch_size`` only names the reference's batching;
-  eigh        torch.linalg.eigh (rocSOLVER, fp64) of the p x p covariance.
+  eigh        torch.linalg.eigh (rocSOLVER, fp64) of the p x p covariance, or with
+              ``solver="native"`` the project's own top-k solver (vr_eigh_top_f64,
+              csrc/eigvals.hip): deterministic, no dependence on a library version, and
+              its vectors already carry the largest-|.|-positive sign.
 Eigenvector signs are solver-defined (numpy's LAPACK eigh in the reference, rocSOLVER here;
 neither makes a sign promise) and are returned raw by default, as the reference does. The
 coarse PCA labels depend on the sign of each projection, so labels derived from these
@@ -110,10 +113,25 @@ def sign_convention(vecs: torch.Tensor) -> torch.Tensor:
     return vecs * s
 
 
-def eig_top(cov: torch.Tensor, n_components: int, normalize_signs: bool = False):
+SOLVERS = ("rocsolver", "native")
+
+
+def eig_top(cov: torch.Tensor, n_components: int, normalize_signs: bool = False, solver: str = "rocsolver"):
     """compute_eigenvectors.py:39-44: eigh, the n_components largest eigenvalues in
     descending order, their vectors (solver signs unless normalize_signs), and the sum of
-    all eigenvalues."""
+    all eigenvalues.
+
+    solver="native": analysis.compute_eigenspectra.eigh_top on a clone of cov. Only the leading
+    pairs are computed, so the total variance is the trace of cov, where the reference sums all
+    eigenvalues; the two agree to 8 p eps ||cov||_F. The vectors come in the sign_convention
+    form whatever normalize_signs says."""
+    if solver not in SOLVERS:
+        raise ValueError(f"solver must be one of {SOLVERS}: got {solver!r}")
+    if solver == "native":
+        from .analysis.compute_eigenspectra import eigh_top
+
+        w, V = eigh_top(cov, min(int(n_components), int(cov.size(0))))
+        return V.cpu().numpy(), w.cpu().numpy(), float(torch.trace(cov))
     vals, vecs = torch.linalg.eigh(cov)
     vals_h = vals.cpu().numpy()
     idx = np.argsort(vals_h)[::-1][:n_components]
@@ -125,19 +143,20 @@ def eig_top(cov: torch.Tensor, n_components: int, normalize_signs: bool = False)
 
 
 def batched_pca(X, n_components: int, batch_size: int = 10000, device: Optional[torch.device] = None,
-                normalize_signs: bool = False):
+                normalize_signs: bool = False, solver: str = "rocsolver"):
     """Drop-in for compute_eigenvectors.batched_pca (:23-44): (components (p, k) float64,
     eigenvalues (k,) float64, mean (p,) float32, total variance). Component signs are the
     solver's (see the module doc; normalize_signs=True for the largest-|.|-positive
-    convention)."""
+    convention; solver as eig_top)."""
     if batch_size <= 0:
         raise ValueError("batch_size must be positive")
     mean, cov = pca_mean_cov(X, device)
-    comps, vals, total = eig_top(cov, n_components, normalize_signs)
+    comps, vals, total = eig_top(cov, n_components, normalize_signs, solver)
     return comps, vals, mean.cpu().numpy(), np.float64(total)
 
 
-def batched_pca_sharded(x_local: torch.Tensor, n_components: int, pg=None, normalize_signs: bool = False):
+def batched_pca_sharded(x_local: torch.Tensor, n_components: int, pg=None, normalize_signs: bool = False,
+                        solver: str = "rocsolver"):
     """batched_pca over row shards (rank r holds rows [sum of earlier shards, +n_r), in
     order). Every rank returns the same (components, eigenvalues, mean, total variance)."""
     x = _device_rows(x_local, None)
@@ -162,7 +181,7 @@ def batched_pca_sharded(x_local: torch.Tensor, n_components: int, pg=None, norma
     dist.all_reduce(part, group=pg)
     # true division (torch divides by a Python scalar as a multiply by its reciprocal)
     cov = part / torch.full_like(part, float(n - 1))
-    comps, vals, total = eig_top(cov, n_components, normalize_signs)
+    comps, vals, total = eig_top(cov, n_components, normalize_signs, solver)
     return comps, vals, mean.cpu().numpy(), np.float64(total)
 
 
@@ -176,6 +195,8 @@ def main(argv=None):
     ap.add_argument("--batch_size", type=int, default=10000)
     ap.add_argument("--normalize_signs", action="store_true",
                     help="largest-|.| component positive (reproducible across solvers); default: raw solver signs")
+    ap.add_argument("--solver", choices=SOLVERS, default="rocsolver",
+                    help="native: the project's own top-k eigensolver, signs fixed; default: torch.linalg.eigh")
     a = ap.parse_args(argv)
     feats = a.features or f"datasets/obj_cls/imagenet/features_{a.model_name}.npz"
     out = a.output or f"datasets/obj_cls/imagenet/eigenvectors_{a.model_name}.npz"
@@ -184,11 +205,13 @@ def main(argv=None):
     data = np.load(feats)  # allow_pickle stays False: features are a plain float32 array
     features = data[f"{a.model_name}_features"]
     print(f"Features shape: {features.shape}")
-    comps, vals, mean, total = batched_pca(features, a.n_components, a.batch_size, normalize_signs=a.normalize_signs)
+    comps, vals, mean, total = batched_pca(features, a.n_components, a.batch_size, normalize_signs=a.normalize_signs,
+                                          solver=a.solver)
     # the sign convention travels with the vectors: the coarse labels flip with a component's
     # sign, so a label set is reproducible only together with this field (extra key; the
     # reference's four keys are unchanged)
-    sign = "largest_abs_positive" if a.normalize_signs else f"raw:rocsolver-syevd torch {torch.__version__}"
+    sign = ("largest_abs_positive:native" if a.solver == "native" else
+            "largest_abs_positive" if a.normalize_signs else f"raw:rocsolver-syevd torch {torch.__version__}")
     np.savez(out, eigenvectors=comps, eigenvalues=vals, mean=mean, total_variance=total,
              sign_convention=np.array(sign))
     print(f"Eigenvectors saved to {out}")

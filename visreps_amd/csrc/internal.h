@@ -135,7 +135,9 @@ enum KtKernel : int {
   KT_KNN_EXACT = 16,  // k_knn_exact_rows (units: pairs scanned)
   KT_EIG_TRIDIAG = 17,  // eigvals.hip stage A: all Householder steps of one call (units: bytes of A22 moved)
   KT_EIG_BISECT = 18,   // eigvals.hip stage B: bounds + bisection (units: Sturm terms)
-  KT_N = 19
+  KT_EIG_INVIT = 19,    // eigvals.hip stage C: shifts, start, inverse iterations + Gram-Schmidt (units: solve steps)
+  KT_EIG_BACK = 20,     // eigvals.hip stage D: k_eigv_back (units: bytes of reflectors read)
+  KT_N = 21
 };
 bool ktimer_on();
 struct KtScope {
