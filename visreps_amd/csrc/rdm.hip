@@ -1206,6 +1206,8 @@ __global__ __launch_bounds__(256) void k_gram_reduce_w(GramParams P) {
 // each wave waits (counted vmcnt) before the barrier of the phase that first reads a
 // stage: P2(t) for the A halves of t+1 (B-right(t+1) may stay in flight), P3(t) for the B
 // halves (B-left(t+2) may). Diagonal super-tiles stage and read the A halves only.
+// Waves 4-7 run the same phases with their MFMAs half a phase late (e_stage_skew), so
+// the two waves of a SIMD do not sit in their issue/read heads at the same time.
 // LDS image of a half-tile: row r's 16-B chunk c at r * 128 + (c ^ ((r >> 1) & 7)) * 16;
 // a fragment read (16 rows of a 16-row block, one chunk per 16 lanes) then touches 16
 // distinct 16-B bank slots in each ds_read_b128 lane group.
@@ -1277,17 +1279,19 @@ __device__ inline void e_read_b(const char* half, int r0, const ELane& o, EFragB
 
 // quadrant (MA, NB) of the wave's block: 4 x 2 tiles of 16 x 16, hh, hl, lh products
 // ONE (bf16 input, raw records of 64 k): hi = k 0..31, lo = k 32..63 of the stage, 2 products
-template <int MA, int NB, bool ONE>
+// [M0, M1): the row blocks taken (a staggered wave runs a quadrant as two halves, see
+// e_stage_skew); each accumulator's own hh, hl, lh order is the same for any range
+template <int MA, int NB, bool ONE, int M0 = 0, int M1 = 4>
 __device__ inline void e_mfma(const EFragA& a, const EFragB& b, f32x4 (&acc)[8][4]) {
 #pragma unroll
-  for (int m = 0; m < 4; ++m)
+  for (int m = M0; m < M1; ++m)
 #pragma unroll
     for (int n = 0; n < 2; ++n)
       acc[MA * 4 + m][NB * 2 + n] =
           __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi[m], b.hi[n], acc[MA * 4 + m][NB * 2 + n], 0, 0, 0);
   if constexpr (ONE) {
 #pragma unroll
-    for (int m = 0; m < 4; ++m)
+    for (int m = M0; m < M1; ++m)
 #pragma unroll
       for (int n = 0; n < 2; ++n)
         acc[MA * 4 + m][NB * 2 + n] =
@@ -1295,13 +1299,13 @@ __device__ inline void e_mfma(const EFragA& a, const EFragB& b, f32x4 (&acc)[8][
     return;
   }
 #pragma unroll
-  for (int m = 0; m < 4; ++m)
+  for (int m = M0; m < M1; ++m)
 #pragma unroll
     for (int n = 0; n < 2; ++n)
       acc[MA * 4 + m][NB * 2 + n] =
           __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi[m], b.lo[n], acc[MA * 4 + m][NB * 2 + n], 0, 0, 0);
 #pragma unroll
-  for (int m = 0; m < 4; ++m)
+  for (int m = M0; m < M1; ++m)
 #pragma unroll
     for (int n = 0; n < 2; ++n)
       acc[MA * 4 + m][NB * 2 + n] =
@@ -1447,7 +1451,98 @@ __device__ inline void e_stage(const GramParams& P, char* lds, int64_t row0, int
   if (P.flush && more1 && (t + 1) % P.flush == 0) e_flush(acc, P.fbuf + (size_t)blockIdx.x * WT * WT, t + 1 == P.flush);
 }
 
-template <bool DIAG, bool ONE>
+// The staggered form of e_stage, run by waves 4-7 (wr == 1), the SIMD partners of waves
+// 0-3. Same barriers, same LDS-DMA pieces and fragment reads in the same barrier interval
+// and order as e_stage (so the counted vmcnt waits stand), but the MFMAs run half a phase
+// late: phase p is barrier; the late half (row blocks m = 2, 3) of phase p-1's quadrant;
+// issue and reads of phase p; the early half (m = 0, 1) of phase p's quadrant. A wave of
+// 0-3 then has its matrix work under its partner's issue/read head and the other way round,
+// instead of both heads and both MFMA runs meeting on the SIMD.
+//  * Results: an accumulator belongs to one (quadrant, m) and still sees hh, hl, lh of
+//    stage t, then of t+1, ...: the same sequence as in e_stage, so bit-identical sums.
+//  * Registers: the late half of phase p-1 uses fragments that phase p's reads overwrite
+//    (P2 reads AX, used by P1; P3 and P0 read the B set the phase before used). The late
+//    MFMAs stand before the reads in program order (pinned by a sched_barrier).
+//  * LDS: the late MFMAs of phase p run after barrier p+1, so "the reads of phase p are
+//    consumed before barrier p+2" no longer shows that they have returned. Instead the
+//    wave waits lgkmcnt(0) before every closing barrier: every LDS read of phase p has
+//    returned at barrier p+1, and a buffer is restaged >= 2 phases after its last read.
+//  * pend: the late half of the previous stage's P3 is still owed. It is false at t = 0
+//    and after a flush, and e_loop pays the last one after the final stage: e_flush,
+//    e_unflush, e_store and e_partial always see whole stages.
+__device__ inline void e_reads_done() {
+  __builtin_amdgcn_sched_barrier(0);  // after the phase's early MFMAs, which cover the reads
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+
+template <bool DIAG, bool ODD, bool ONE>
+__device__ inline void e_stage_skew(const GramParams& P, char* lds, int64_t row0, int64_t col0, int t, int ns,
+                                    const ELane& o, const uint32_t (&io)[2], EFragA& AX, EFragA& AY,
+                                    EFragB& BP, EFragB& BQ, f32x4 (&acc)[8][4], bool& pend) {
+  const int wid = threadIdx.x >> 6;
+  const int wr = wid >> 2, wc = wid & 3;
+  EFragB& B0 = ODD ? BQ : BP;  // b0 of this stage
+  EFragB& B1 = ODD ? BP : BQ;  // b1 of this stage, then b0 of the next; b0 of the last stage on entry
+  char* cur = lds + (t & 1) * E_STAGE;
+  char* nxt = lds + ((t + 1) & 1) * E_STAGE;
+  const int ha = wr, hb = DIAG ? (wc >> 1) : 2 + (wc >> 1);
+  const int rb = (wc & 1) * 64;
+  const bool more1 = t + 1 < ns, more2 = t + 2 < ns;
+  // P0: late a1 b0 of t-1 (its b0 sits in B1's registers until the read below); early a0 b0
+  e_barrier();
+  if (pend) e_mfma<1, 0, ONE, 2, 4>(AY, B1, acc);
+  __builtin_amdgcn_sched_barrier(0);
+  if (more1) e_issue(P, nxt, 1, row0, col0, t + 1, io);
+  e_read_b(cur + hb * E_HALF, rb + 32, o, B1);
+  e_mfma<0, 0, ONE, 0, 2>(AX, B0, acc);
+  e_reads_done();
+  // P1: late a0 b0; early a0 b1
+  e_barrier();
+  e_mfma<0, 0, ONE, 2, 4>(AX, B0, acc);
+  __builtin_amdgcn_sched_barrier(0);
+  if (!DIAG && more1) e_issue(P, nxt, 3, row0, col0, t + 1, io);
+  e_read_a(cur + ha * E_HALF, 64, o, AY);
+  e_mfma<0, 1, ONE, 0, 2>(AX, B1, acc);
+  e_reads_done();
+  // P2: late a0 b1 (AX, before a0(t+1) is read into it); early a1 b1
+  if (more1) {
+    if (DIAG)
+      p_wait<0>();
+    else
+      p_wait<2>();
+  }
+  e_barrier();
+  e_mfma<0, 1, ONE, 2, 4>(AX, B1, acc);
+  __builtin_amdgcn_sched_barrier(0);
+  if (!DIAG && more2) e_issue(P, cur, 2, row0, col0, t + 2, io);
+  if (more1) e_read_a(nxt + ha * E_HALF, 0, o, AX);
+  e_mfma<1, 1, ONE, 0, 2>(AY, B1, acc);
+  e_reads_done();
+  // P3: late a1 b1 (B1, before b0(t+1) is read into it); early a1 b0
+  if (!DIAG && more1) {
+    if (more2)
+      p_wait<2>();
+    else
+      p_wait<0>();
+  }
+  e_barrier();
+  e_mfma<1, 1, ONE, 2, 4>(AY, B1, acc);
+  __builtin_amdgcn_sched_barrier(0);
+  if (more2) e_issue(P, cur, 0, row0, col0, t + 2, io);
+  if (more1) e_read_b(nxt + hb * E_HALF, rb, o, B1);
+  e_mfma<1, 0, ONE, 0, 2>(AY, B0, acc);
+  e_reads_done();
+  pend = true;
+  if (P.flush && more1 && (t + 1) % P.flush == 0) {
+    e_mfma<1, 0, ONE, 2, 4>(AY, B0, acc);  // the stage whole before its sums leave the registers
+    pend = false;
+    e_flush(acc, P.fbuf + (size_t)blockIdx.x * WT * WT, t + 1 == P.flush);
+  }
+}
+
+// SKEW: the waves 4-7 form (e_stage_skew). Both forms pass one barrier in the prologue and
+// four per stage.
+template <bool DIAG, bool ONE, bool SKEW>
 __device__ inline void e_loop(const GramParams& P, char* lds, int64_t row0, int64_t col0, int ns,
                               f32x4 (&acc)[8][4]) {
   const int wid = threadIdx.x >> 6;
@@ -1478,6 +1573,22 @@ __device__ inline void e_loop(const GramParams& P, char* lds, int64_t row0, int6
   EFragB BP, BQ;
   e_read_a(lds + ha * E_HALF, 0, o, AX);
   e_read_b(lds + hb * E_HALF, rb, o, BP);
+  if constexpr (SKEW) {
+    bool pend = false;
+    for (int t = 0; t < ns; t += 2) {
+      e_stage_skew<DIAG, false, ONE>(P, lds, row0, col0, t, ns, o, io, AX, AY, BP, BQ, acc, pend);
+      if (t + 1 < ns)
+        e_stage_skew<DIAG, true, ONE>(P, lds, row0, col0, t + 1, ns, o, io, AX, AY, BP, BQ, acc, pend);
+    }
+    // the half still owed: a1 b0 of the last stage (b0 in BP after an even ns - 1, else BQ)
+    if (pend) {
+      if (ns & 1)
+        e_mfma<1, 0, ONE, 2, 4>(AY, BP, acc);
+      else
+        e_mfma<1, 0, ONE, 2, 4>(AY, BQ, acc);
+    }
+    return;
+  }
   for (int t = 0; t < ns; t += 2) {
     e_stage<DIAG, false, ONE>(P, lds, row0, col0, t, ns, o, io, AX, AY, BP, BQ, acc);
     if (t + 1 < ns) e_stage<DIAG, true, ONE>(P, lds, row0, col0, t + 1, ns, o, io, AX, AY, BP, BQ, acc);
@@ -1497,6 +1608,26 @@ __device__ inline void e_partial(const GramParams& P, f32x4 (&acc)[8][4], int sp
       for (int e = 0; e < 4; ++e) out[(wr * 128 + i * 16 + 4 * g + e) * WT + wc * 64 + j * 16 + l16] = acc[i][j][e];
 }
 
+// One wave's 128 x 64 block of a super-tile (or of its k split): loop, flushed sums, epilogue
+template <bool ONE, bool SKEW>
+__device__ inline void e_tile(const GramParams& P, const GramParams& S, char* lds, int64_t row0, int64_t col0,
+                              int ns, bool diag, int split, int ltile) {
+  f32x4 acc[8][4];
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (diag)
+    e_loop<true, ONE, SKEW>(S, lds, row0, col0, ns, acc);
+  else
+    e_loop<false, ONE, SKEW>(S, lds, row0, col0, ns, acc);
+  if (P.flush && ns > P.flush) e_unflush(acc, P.fbuf + (size_t)blockIdx.x * WT * WT);
+  if (P.splits == 1)
+    e_store<ONE>(P, acc, row0, col0, diag);
+  else
+    e_partial(P, acc, split, ltile);
+}
+
 // Launch position id -> (super-tile, k split) as k_gram3p: split-major; one split = the
 // whole depth (P.kslice = nstage * GK).
 template <bool ONE>
@@ -1513,20 +1644,12 @@ __global__ __launch_bounds__(W_THREADS, 1) void k_gram3e(GramParams P) {
   const int ns = (int)(P.nstage - st0 < sper ? P.nstage - st0 : sper);
   GramParams S = P;
   S.planes = P.planes + st0 * 64;  // records of stage st0 onwards (the row stride stays nstage)
-  f32x4 acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (diag)
-    e_loop<true, ONE>(S, lds, row0, col0, ns, acc);
+  // waves 4-7 (wr == 1) take the staggered form of the loop. The two forms share no code
+  // after this point (one merged tail costs registers the loop does not have).
+  if (__builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8))
+    e_tile<ONE, true>(P, S, lds, row0, col0, ns, diag, split, ltile);
   else
-    e_loop<false, ONE>(S, lds, row0, col0, ns, acc);
-  if (P.flush && ns > P.flush) e_unflush(acc, P.fbuf + (size_t)blockIdx.x * WT * WT);
-  if (P.splits == 1)
-    e_store<ONE>(P, acc, row0, col0, diag);
-  else
-    e_partial(P, acc, split, ltile);
+    e_tile<ONE, false>(P, S, lds, row0, col0, ns, diag, split, ltile);
 }
 
 // The full-depth wide launches run k_gram3e (measured +3.5-8.5 % over k_gram3p on whole
