@@ -650,6 +650,81 @@ int vr_eigh_top_f64(double* A, int64_t m, int64_t lda, int64_t k, double* w, dou
                     void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------
+ * PLS-SVD cross-decomposition (csrc/xcov.hip; analysis/cross_decomposition.py). Replaces, in
+ * visreps/analysis/cross_decomposition.py, GaussianRandomProjection.fit_transform (30-34, 46),
+ * the per-fold PLSSVD(..).fit / .transform of the shuffled KFold (49, 60-75) and the
+ * per-component np.corrcoef / np.cov of the test scores (78-79). Every kernel runs on the fp64
+ * MFMA or in fp64, adds in a fixed order (no float atomics: bit-identical run to run), launches
+ * on the caller's stream and never synchronises with the host; trip counts depend on shapes and
+ * segment lengths alone.
+ * -------------------------------------------------------------------------- */
+/* G[i, j] = sum_k ((double)A[a_rows[i], k] - a_mean[k]) * B[j, k]: both operands K-contiguous
+ * (NT). A [dev] fp32 with leading dimension lda >= K; a_rows [dev] M int32 (nullable: row i);
+ * a_mean [dev] K doubles (nullable: 0). B [dev] N x K, leading dimension ldb >= K, fp32
+ * (b_f64 = 0) or fp64 (b_f64 = 1). G [dev] M x N, leading dimension ldg >= N, fp64 (g_f64 = 1)
+ * or fp32 (g_f64 = 0: the fp64 sum rounded once). Products of two fp32 values are exact in
+ * fp64. Split-K partials are added in slice order. Rows of A or B that are not 16-byte
+ * aligned (pointer or leading dimension) take scalar loads. The projection Z = X R^T of
+ * GaussianRandomProjection.transform is b_f64 = 0, g_f64 = 0 with R cast to fp32 (the cast
+ * scikit-learn applies for float32 X). M = 0 or N = 0 writes nothing; K >= 1. VR_EINVAL for
+ * a bad shape or a null pointer, VR_EWORKSPACE below vr_xgemm_nt_workspace(M, N, K). */
+size_t vr_xgemm_nt_workspace(int64_t M, int64_t N, int64_t K);
+int vr_xgemm_nt_f32(const float* A, int64_t M, int64_t K, int64_t lda, const int32_t* a_rows,
+                    const double* a_mean, const void* B, int b_f64, int64_t N, int64_t ldb, void* G,
+                    int g_f64, int64_t ldg, void* ws, size_t ws_bytes, void* stream);
+
+/* Segmented cross-moments: the one pass over the data that every fold's training
+ * cross-covariance follows from (cross_decomposition.py:62-72 reads 7/8 of the rows K times).
+ * X [dev] fp32 (., p) ldx >= p and Y [dev] fp32 (., q) ldy >= q share their rows; rows [dev]
+ * int32 (nullable: the identity) lists them in fold order, seg [host] F + 1 offsets into that
+ * order with seg[0] = 0 (segment f = positions seg[f] .. seg[f + 1]); mean_x, mean_y [dev]
+ * fp64 column means over all rows (vr_col_mean_f64). Writes
+ *   S     [dev] F x p x q doubles, S[f] = sum over segment f of (x - mean_x)^T (y - mean_y)
+ *   stats [dev] F x 2 x (p + q) doubles (nullable): [f][0] the column sums, [f][1] the sums of
+ *         squares of the same centred values, X's columns then Y's.
+ * An empty segment gives all zeros. 1 <= F <= 65535. VR_EWORKSPACE below
+ * vr_xcov_segments_workspace(p, q, F, longest segment). */
+size_t vr_xcov_segments_workspace(int64_t p, int64_t q, int64_t F, int64_t max_seg);
+int vr_xcov_segments_f32(const float* X, int64_t ldx, const float* Y, int64_t ldy, int64_t p, int64_t q,
+                         const int32_t* rows, const int64_t* seg, int64_t F, const double* mean_x,
+                         const double* mean_y, double* S, double* stats, void* ws, size_t ws_bytes,
+                         void* stream);
+
+/* The standardised training cross-covariance of every fold from the segment moments (what
+ * PLSSVD.fit forms as X_s^T Y_s after _center_scale_xy): with T = sum_f S[f], n_tr = n - n_f,
+ * m and s the training mean (about the global mean) and ddof=1 standard deviation from stats
+ * (s = 0 replaced by 1),  C[f] = (T - S[f] - n_tr m_x m_y^T) / (s_x s_y^T).  C [dev] F x p x q
+ * doubles. Every fold must leave at least 2 training rows. */
+size_t vr_fold_xcov_workspace(int64_t p, int64_t q);
+int vr_fold_xcov_f64(const double* S, const double* stats, const int64_t* seg, int64_t F, int64_t p,
+                     int64_t q, const double* mean_x, const double* mean_y, double* C, void* ws,
+                     size_t ws_bytes, void* stream);
+
+/* PLS-SVD of folds 0 .. n_run - 1 (n_run <= F): for each, C[f] as above is written as the
+ * symmetric J = [[0, C], [C^T, 0]] of order p + q <= 65536, whose k largest eigenpairs
+ * (vr_eigh_top_f64) are sigma_j and [u_j; v_j] / sqrt(2); each half is normalised in fp64, given
+ * svd_flip's u-based sign (largest |u| entry positive, lowest index on a tie) and divided by the
+ * training standard deviation; the fold's test rows are scored, (z - training mean) . u / s,
+ * and each paired score column gives Pearson r and the ddof=1 covariance (two passes). Arguments
+ * as vr_xcov_segments_f32, S and stats from it; 1 <= k <= min(p, q). Outputs, [dev]:
+ *   corr, cov, sigma  n_run x k doubles;  null  n_run x k int32: 1 where
+ *         sigma_j <= 64 (p + q) eps sigma_1 (a component past the rank of C, whose vectors
+ *         LAPACK leaves arbitrary): its corr and cov are NaN
+ *   imbalance (nullable) n_run x k doubles: |2 |u|^2 - 1| before normalisation
+ *   weights (nullable) k x (p + q) doubles: fold wfold's unit u_j then unit v_j per row, with
+ *         wmean and wstd (p + q doubles each) its training means and standard deviations.
+ * A test fold of fewer than 2 rows gives NaN corr and cov; a non-finite input gives NaN
+ * everywhere. VR_EINVAL if a fold leaves fewer than 2 training rows; VR_EWORKSPACE below
+ * vr_plssvd_folds_workspace(p, q, k, longest test fold among those run). */
+size_t vr_plssvd_folds_workspace(int64_t p, int64_t q, int64_t k, int64_t max_test);
+int vr_plssvd_folds_f64(const float* X, int64_t ldx, const float* Y, int64_t ldy, int64_t p, int64_t q,
+                        const int32_t* rows, const int64_t* seg, int64_t F, int64_t n_run,
+                        const double* mean_x, const double* mean_y, const double* S, const double* stats,
+                        int64_t k, double* corr, double* cov, double* sigma, int32_t* null,
+                        double* imbalance, int64_t wfold, double* weights, double* wmean, double* wstd,
+                        void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------
  * Host: legacy numpy RandomState (MT19937) index streams, bit-exact.
  * Replaces np.random.RandomState(seed) + .choice(n, k, replace=False) / .permutation(n)
  * (evals.py:260-261,356,362-364; rsa.py:169,176,248-250; evals.py:111-113).
@@ -660,6 +735,12 @@ int vr_rng_seed(void* state, uint32_t seed);                /* RandomState(seed)
 int vr_rng_permutation(void* state, int64_t n, int32_t* out); /* .permutation(n) */
 int vr_rng_choice(void* state, int64_t n, int64_t k, int32_t* out); /* .choice(n,k,replace=False) */
 int vr_rng_random_u32(void* state, int64_t count, uint32_t* out);   /* raw MT19937 draws */
+/* .normal(loc, scale, count), bit for bit (legacy_gauss: the polar method on pairs of 53-bit
+ * doubles ((a >> 5) 2^26 + (b >> 6)) / 2^53, x = 2 u - 1, r2 >= 1 or r2 == 0 rejected,
+ * f = sqrt(-2 log(r2) / r2); a call returns f x2 and the state keeps f x1 for the next, cleared
+ * by vr_rng_seed; the value is loc + scale g). The stream behind scikit-learn's
+ * _gaussian_random_matrix (GaussianRandomProjection, cross_decomposition.py:30-31). out [host]. */
+int vr_rng_normal_f64(void* state, int64_t count, double loc, double scale, double* out);
 /* Convenience: fresh RandomState(seed), then n_draws successive choice(n, k) calls
  * into out (n_draws, k) [host]. */
 int vr_legacy_choice(uint32_t seed, int64_t n, int64_t k, int64_t n_draws, int32_t* out);

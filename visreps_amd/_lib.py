@@ -254,6 +254,29 @@ _PROTOTYPES = {
     "vr_rng_permutation": (ctypes.c_int, [_vp, _c_i64, _vp]),
     "vr_rng_choice": (ctypes.c_int, [_vp, _c_i64, _c_i64, _vp]),
     "vr_rng_random_u32": (ctypes.c_int, [_vp, _c_i64, _vp]),
+    "vr_rng_normal_f64": (ctypes.c_int, [_vp, _c_i64, ctypes.c_double, ctypes.c_double, _vp]),
+    "vr_xgemm_nt_workspace": (_c_sz, [_c_i64, _c_i64, _c_i64]),
+    "vr_xgemm_nt_f32": (
+        ctypes.c_int,
+        [_vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, ctypes.c_int, _c_i64, _c_i64, _vp, ctypes.c_int, _c_i64,
+         _vp, _c_sz, _vp],
+    ),
+    "vr_xcov_segments_workspace": (_c_sz, [_c_i64, _c_i64, _c_i64, _c_i64]),
+    "vr_xcov_segments_f32": (
+        ctypes.c_int,
+        [_vp, _c_i64, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp],
+    ),
+    "vr_fold_xcov_workspace": (_c_sz, [_c_i64, _c_i64]),
+    "vr_fold_xcov_f64": (
+        ctypes.c_int,
+        [_vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _c_sz, _vp],
+    ),
+    "vr_plssvd_folds_workspace": (_c_sz, [_c_i64, _c_i64, _c_i64, _c_i64]),
+    "vr_plssvd_folds_f64": (
+        ctypes.c_int,
+        [_vp, _c_i64, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _c_i64,
+         _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _c_sz, _vp],
+    ),
     "vr_legacy_choice": (ctypes.c_int, [ctypes.c_uint32, _c_i64, _c_i64, _c_i64, _vp]),
     "vr_percentile_linear": (ctypes.c_double, [_vp, _c_i64, ctypes.c_double]),
 }

@@ -56,6 +56,8 @@ int num_cus() {
 struct MTState {
   uint32_t mt[624];
   int pos;
+  int has_gauss;  // legacy_gauss keeps the second variate of a polar pair for the next call
+  double gauss;
 };
 
 static void mt_seed(MTState* s, uint32_t seed) {
@@ -63,6 +65,8 @@ static void mt_seed(MTState* s, uint32_t seed) {
   for (int i = 1; i < 624; ++i)
     s->mt[i] = 1812433253u * (s->mt[i - 1] ^ (s->mt[i - 1] >> 30)) + (uint32_t)i;
   s->pos = 624;
+  s->has_gauss = 0;
+  s->gauss = 0.0;
 }
 
 static inline uint32_t mt_twist(uint32_t a, uint32_t b, uint32_t c) {
@@ -104,6 +108,34 @@ static inline uint32_t mt_interval(MTState* s, uint32_t mx) {
   while ((v = (mt_next(s) & mask)) > mx) {
   }
   return v;
+}
+
+// random_sample's 53-bit double from two raw draws
+static inline double mt_double(MTState* s) {
+  const uint32_t a = mt_next(s) >> 5, b = mt_next(s) >> 6;
+  return ((double)a * 67108864.0 + (double)b) / 9007199254740992.0;
+}
+
+// legacy_gauss: Marsaglia's polar method; returns f x2 and keeps f x1. No contraction: numpy
+// rounds every product (x1 x1 + x2 x2 as two products and a sum).
+static inline double mt_gauss(MTState* s) {
+#pragma clang fp contract(off)
+  if (s->has_gauss) {
+    const double g = s->gauss;
+    s->has_gauss = 0;
+    s->gauss = 0.0;
+    return g;
+  }
+  double x1, x2, r2;
+  do {
+    x1 = 2.0 * mt_double(s) - 1.0;
+    x2 = 2.0 * mt_double(s) - 1.0;
+    r2 = x1 * x1 + x2 * x2;
+  } while (r2 >= 1.0 || r2 == 0.0);
+  const double f = std::sqrt(-2.0 * std::log(r2) / r2);
+  s->gauss = f * x1;
+  s->has_gauss = 1;
+  return f * x2;
 }
 
 static void mt_permutation(MTState* s, int64_t n, int32_t* out) {
@@ -155,6 +187,17 @@ int vr_rng_random_u32(void* state, int64_t count, uint32_t* out) {
   VR_REQUIRE(state != nullptr && (out != nullptr || count == 0), "vr_rng_random_u32: null pointer");
   MTState* s = static_cast<MTState*>(state);
   for (int64_t i = 0; i < count; ++i) out[i] = mt_next(s);
+  return VR_OK;
+}
+
+int vr_rng_normal_f64(void* state, int64_t count, double loc, double scale, double* out) {
+  VR_REQUIRE(state != nullptr && (out != nullptr || count == 0), "vr_rng_normal_f64: null pointer");
+  VR_REQUIRE(count >= 0, "vr_rng_normal_f64: count=%lld", (long long)count);
+  MTState* s = static_cast<MTState*>(state);
+  for (int64_t i = 0; i < count; ++i) {
+#pragma clang fp contract(off)
+    out[i] = loc + scale * mt_gauss(s);  // numpy: loc + scale * gauss, two roundings
+  }
   return VR_OK;
 }
 
