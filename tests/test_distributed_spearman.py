@@ -3,8 +3,10 @@ in its count-table form and its sample-sort form. CPU: gloo world 2 and 3, pairs
 ranks at random, the device pieces (sort keys, radix sort, midranks, per-key counts, table
 midranks, exact dot) emulated in numpy; the collectives, key range, table all-reduce,
 splitters, bucket exchange, global offsets and owner routing are the product code; the score
-must equal the oracle's midrank Spearman. GPU: world 1 through the HIP pieces equals
-spearman_full bit for bit."""
+must equal the oracle's midrank Spearman; the integer sample positions, and world 1 of both
+methods at 17,997,000 pairs, where float32 positions ran one past the keys. GPU: world 1
+through the HIP pieces equals spearman_full bit for bit (the pieces one by one, and composed
+over simulated ranks: test_rank_pieces.py)."""
 import os
 import socket
 
@@ -16,6 +18,13 @@ import torch.multiprocessing as mp
 
 from oracle import rsa_oracle as O
 from visreps_amd.analysis import distributed_spearman as DS
+
+
+def _tie_term(sizes):
+    """sum (k^3 - k) over group sizes as a Python int: one term per distinct size, so tens of
+    millions of groups cost no Python loop."""
+    ks, c = np.unique(np.asarray(sizes, dtype=np.int64), return_counts=True)
+    return sum(int(n) * (int(k) ** 3 - int(k)) for k, n in zip(ks, c))
 
 
 class NumpyRankKernels(DS.RankKernels):
@@ -43,8 +52,7 @@ class NumpyRankKernels(DS.RankKernels):
         gs = np.repeat(starts, ends - starts)
         ge = np.repeat(ends, ends - starts)
         y = 2 * int(base) + gs + ge + 1
-        tie = sum(int(e - s) ** 3 - int(e - s) for s, e in zip(starts, ends))
-        return torch.from_numpy(y.astype(np.int64)), tie
+        return torch.from_numpy(y.astype(np.int64)), _tie_term(ends - starts)
 
     @staticmethod
     def counts(keys, kmin, bins):
@@ -57,12 +65,25 @@ class NumpyRankKernels(DS.RankKernels):
         start = np.concatenate([[0], np.cumsum(c)])[:-1]  # exclusive, bins + 1 entries
         k = keys.numpy().view(np.uint32).astype(np.int64) - int(kmin)
         y = start[k] + start[k + 1] + 1
-        tie = sum(int(v) ** 3 - int(v) for v in c[c > 1])
-        return torch.from_numpy(y.astype(np.int64)), tie
+        return torch.from_numpy(y.astype(np.int64)), _tie_term(c)
 
     @staticmethod
     def dot(a, b):
-        return int(np.dot(a.numpy().astype(object), b.numpy().astype(object)))
+        return exact_dot_u64(a.numpy().view(np.uint64), b.numpy().view(np.uint64))
+
+
+def exact_dot_u64(a, b):
+    """sum a[i] b[i] of uint64 arrays as a Python int, exact for any values and fewer than
+    2^32 elements: 32-bit halves, each half product (< 2^64) summed as its own two halves."""
+    lo32 = np.uint64(0xFFFFFFFF)
+    s32 = np.uint64(32)
+
+    def part(x, y):
+        p = x * y
+        return int((p & lo32).sum(dtype=np.uint64)) + (int((p >> s32).sum(dtype=np.uint64)) << 32)
+
+    al, ah, bl, bh = a & lo32, a >> s32, b & lo32, b >> s32
+    return part(al, bl) + ((part(al, bh) + part(ah, bl)) << 32) + (part(ah, bh) << 64)
 
 
 def _free_port():
@@ -126,6 +147,45 @@ def test_gloo_tables_fall_back_to_sample_sort_beyond_the_cap(tmp_path):
     got = [float((tmp_path / f"r{r}.txt").read_text()) for r in range(world)]
     ref = O.midrank_spearman(_tri(n, seed), _tri(n, seed + 1))
     assert got[0] == got[1] and abs(got[0] - ref) <= 1e-12
+
+
+def test_exact_dot_u64_helper_equals_python_ints():
+    g = np.random.default_rng(5)
+    a = g.integers(0, 1 << 64, 1000, dtype=np.uint64)
+    b = g.integers(0, 1 << 64, 1000, dtype=np.uint64)
+    a[:4] = b[:4] = (1 << 64) - 1
+    assert exact_dot_u64(a, b) == sum(int(x) * int(y) for x, y in zip(a, b))
+    assert exact_dot_u64(a[:0], b[:0]) == 0
+
+
+@pytest.mark.parametrize("s", [32, 64, 96, 256])
+@pytest.mark.parametrize("m", [1, 2, 31, 32, 33, (1 << 24) + 3, 17_997_000, 49_995_000, 2_664_463_500,
+                               (1 << 32) - 1])
+def test_sample_positions_are_exact_integers(m, s):
+    # float32 linspace rounds its end point past m - 1 beyond 2^24 (+1 at M = 17,997,000,
+    # +117 at M = 2,664,463,500); the integer form cannot
+    p = DS._sample_positions(m, s, torch.device("cpu"))
+    assert p.dtype == torch.int64 and p.shape == (s,)
+    q = p.tolist()
+    assert q[0] == 0 and q[-1] == m - 1
+    assert all(x <= y for x, y in zip(q, q[1:]))
+    assert all(0 <= x <= m - 1 for x in q)
+    assert q == [i * (m - 1) // (s - 1) for i in range(s)]
+
+
+@pytest.mark.slow  # about 30 s of numpy sorts and rankdata over 18M pairs
+def test_sample_sort_beyond_2_24_pairs_world1_numpy():
+    # M = 17,997,000 (the n = 6000 triangle): the float32 sample positions ended at M, one
+    # past the last key, and indexing raised IndexError. rand()'s key range exceeds
+    # TABLE_CAP, so method="tables" takes the sample sort as well.
+    M = 17_997_000
+    a = np.random.RandomState(61).rand(M).astype(np.float32)
+    b = np.random.RandomState(62).rand(M).astype(np.float32)
+    t = torch.arange(M)
+    got = {m: DS.distributed_spearman(torch.from_numpy(a), t, torch.from_numpy(b), t, M, None, NumpyRankKernels(),
+                                      method=m) for m in ("sort", "tables")}
+    assert got["sort"] == got["tables"]
+    assert abs(got["sort"] - O.midrank_spearman(a, b)) <= 1e-12
 
 
 @pytest.mark.gpu

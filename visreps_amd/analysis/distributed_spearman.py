@@ -149,6 +149,13 @@ def _allreduce_int(v: int, dev, pg) -> int:
     return sum(int(x) << (16 * i) for i, x in enumerate(limbs.cpu().tolist()))
 
 
+def _sample_positions(m: int, s: int, device) -> torch.Tensor:
+    """s >= 2 regular positions in [0, m - 1] (m >= 1), non-decreasing, first 0 and last
+    m - 1, in integer arithmetic: float32 linspace rounds its end point past m - 1 once
+    m - 1 > 2^24, and the last sample then indexes out of bounds."""
+    return torch.arange(s, dtype=torch.int64, device=device) * (m - 1) // (s - 1)
+
+
 def global_midranks(values: torch.Tensor, tidx: torch.Tensor, M: int, pg=None,
                     kernels: RankKernels = None) -> Tuple[torch.Tensor, int]:
     """Doubled global average ranks of this rank's t range [M r / W, M (r+1) / W) (dense,
@@ -162,7 +169,7 @@ def global_midranks(values: torch.Tensor, tidx: torch.Tensor, M: int, pg=None,
     # 2. splitters from regular samples of every rank's sorted keys
     s = 32 * world
     m = ku.numel()
-    samp = ku[torch.linspace(0, max(m - 1, 0), s, device=dev).long()] if m else torch.zeros(0, dtype=torch.int64, device=dev)
+    samp = ku[_sample_positions(m, s, dev)] if m else torch.zeros(0, dtype=torch.int64, device=dev)
     cnt = torch.tensor([samp.numel()], dtype=torch.int64, device=dev)
     if world > 1:
         sizes = [torch.zeros_like(cnt) for _ in range(world)]
@@ -174,7 +181,7 @@ def global_midranks(values: torch.Tensor, tidx: torch.Tensor, M: int, pg=None,
         dist.all_gather(allb, buf, group=pg)
         pool = torch.cat(allb)
         pool = torch.sort(pool[pool >= 0]).values
-        spl = pool[torch.linspace(0, pool.numel() - 1, world + 1, device=dev).long()[1:-1]] if pool.numel() else pool
+        spl = pool[_sample_positions(pool.numel(), world + 1, dev)[1:-1]] if pool.numel() else pool
     else:
         spl = torch.zeros(0, dtype=torch.int64, device=dev)
     # 3. bucket b = number of splitters strictly below the key (a function of the key)
@@ -268,11 +275,18 @@ def distributed_spearman(a_values: torch.Tensor, a_tidx: torch.Tensor, b_values:
     ya, ta = ranks(a_values, a_tidx, M, pg, K)
     yb, tb = ranks(b_values, b_tidx, M, pg, K)
     ab = _allreduce_int(K.dot(ya, yb), dev, pg)
+    return _rho_from_sums(ab, ta, tb, M)
+
+
+def _rho_from_sums(ab: int, ta: int, tb: int, M: int) -> float:
+    """rho from the exact sum of yA yB over the M pairs (doubled midranks) and the two tie
+    terms sum (k^3 - k): the engine's formula, NaN for fewer than two pairs or a constant
+    triangle."""
     mu = M * (M + 1) ** 2
     sq = 4 * (M * (M + 1) * (2 * M + 1) // 6)
     va = sq - ta // 3 - mu
     vb = sq - tb // 3 - mu
-    if int(nan.item()) or M < 2 or va <= 0 or vb <= 0:
+    if M < 2 or va <= 0 or vb <= 0:
         return float("nan")
     r = _f64(ab - mu) / math.sqrt(_f64(va) * _f64(vb))
     return max(-1.0, min(1.0, r))
