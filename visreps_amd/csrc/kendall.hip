@@ -745,8 +745,10 @@ static int run_kendall(const PlanView& A, const PlanView& B, int64_t n, const in
   VR_CHECK_LAUNCH();
   VR_CHECK_HIP(hipEventRecord(side->in, st));  // the level-0 stream exists: preparation may start
   // x-lex tie streams (only when A has multi-element groups)
-  // (fused into the top level's walk below unless VISREPS_KENDALL_TOP3=0)
-  static const bool top3 = !(getenv("VISREPS_KENDALL_TOP3") && atoi(getenv("VISREPS_KENDALL_TOP3")) == 0);
+  // (fused into the top level's walk below unless VISREPS_KENDALL_TOP3=0; read on every call,
+  // as kendall_cfg reads VISREPS_KENDALL_MASKS)
+  const char* e3 = getenv("VISREPS_KENDALL_TOP3");
+  const bool top3 = !(e3 && atoi(e3) == 0);
   const bool xties = hx.max_group > 1;
   if (xties) {
     k_xlex_flags<<<gbW, 256, 0, st>>>(W.keys, W.ey[0], M, W.xa_start, W.xa_mem, W.xj_start, W.xj_mem);
