@@ -38,6 +38,7 @@ extern "C" {
 #define VR_EHIP (-2)      /* HIP runtime error */
 #define VR_EWORKSPACE (-3) /* workspace smaller than the *_workspace() query */
 #define VR_EINTERNAL (-4)  /* an exact-arithmetic invariant of the result failed (a bug) */
+#define VR_ENOCONV (-5)    /* an iteration hit its cap before converging; outputs hold the last iterate */
 
 /* Library version (major*10000 + minor*100 + patch). */
 int vr_version(void);
@@ -259,7 +260,9 @@ int64_t vr_engine_est1_fallbacks(void);
 // 13 .. 16 the nearest-neighbour search of vr_knn2_f32: staging, k_knn_cand (units: FLOPs of the
 // tiles walked), merge + rerank, k_knn_exact_rows; 17 .. 20 the symmetric eigensolver: stage A
 // (units: bytes of A22 moved), bounds + bisection, and for vr_eigh_top_f64 the inverse iterations
-// (stage C) and the back-transformation (stage D).
+// (stage C) and the back-transformation (stage D); 21 .. 23 the Jacobi SVD of vr_svd_jacobi_f64:
+// staging (transpose, R = I, first row norms), all the step launches of one sweep (units: FLOPs
+// of a full sweep, 3 n^2 L per member; the replay on R runs inside the step kernel), finish.
 // units: pairs walked (engine kernels) or tile FLOPs 2 d x tile elements (Gram kernels).
 // No reference counterpart (the reference has no native kernels).
 int vr_ktimer_enable(int on);
@@ -723,6 +726,59 @@ int vr_plssvd_folds_f64(const float* X, int64_t ldx, const float* Y, int64_t ldy
                         int64_t k, double* corr, double* cov, double* sigma, int32_t* null,
                         double* imbalance, int64_t wfold, double* weights, double* wmean, double* wstd,
                         void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------
+ * Batched one-sided (Hestenes) Jacobi SVD in fp64 (csrc/svd.hip): the dense solver of PLS-SVD's
+ * solver="jacobi". Replaces the scipy.linalg.svd inside PLSSVD.fit
+ * (visreps/analysis/cross_decomposition.py:66) for all folds in one call.
+ * -------------------------------------------------------------------------- */
+/* The thin SVD of `batch` matrices. A [dev] member b at A + b stride_a, p x q row-major with
+ * leading dimension lda >= q; never written. With r = min(p, q), outputs [dev]:
+ *   S      batch x r doubles, descending (equal values in the order of their rows)
+ *   U      batch x r x p doubles, row j = the unit left vector u_j
+ *   Vt     batch x r x q doubles, row j = the unit right vector v_j
+ *   null   batch x r int32: 1 where sigma_j <= 64 (p + q) eps sigma_1; both vectors of such a
+ *          component are NaN
+ *   sweeps batch int32: sweeps the member ran, the last one (no rotation) included
+ * Signs follow svd_flip's u-based rule: the largest |u_j| entry is positive, the lowest index on
+ * a tie. Rotations work on the rows of B = A (p <= q) or A^T, in LDS, in blocks of 8 rows (4
+ * above a long side of 1024, 2 above 2048); max(p, q) > 4096 is VR_EINVAL. One launch per step
+ * of the block-pair schedule (vr_jacobi_schedule), and after every sweep the host reads the
+ * members' done flags with one blocking copy on `stream`: the call synchronises with the host.
+ * A member stops at its first sweep without a rotation; a member that still rotates in sweep 60
+ * makes the call return VR_ENOCONV after writing the last iterate. A member with a non-finite
+ * entry (or whose squared norms overflow) runs no sweep: NaN in S, U and Vt, null = 1,
+ * sweeps = 0; the others are unaffected. No floating-point atomics: a member's result is
+ * bit-identical run to run and does not depend on the batch it is solved in. sigma is accurate
+ * to order (p + q) eps sigma_1, U U^T and Vt Vt^T to order (p + q) eps over the non-null
+ * components, whatever the spacing of the singular values. batch = 0 writes nothing; batch <=
+ * 65535. VR_EWORKSPACE below vr_svd_jacobi_workspace(batch, p, q). */
+size_t vr_svd_jacobi_workspace(int64_t batch, int64_t p, int64_t q);
+int vr_svd_jacobi_f64(const double* A, int64_t batch, int64_t p, int64_t q, int64_t lda, int64_t stride_a,
+                      double* S, double* U, double* Vt, int32_t* null, int32_t* sweeps, void* ws,
+                      size_t ws_bytes, void* stream);
+/* Host. The block-pair schedule of one sweep over nb >= 1 blocks: a round-robin tournament
+ * (circle method) over nb_even = nb + (nb odd) blocks. pairs [host]
+ * (nb_even - 1) x (nb_even / 2) x 2 int32: step s, pair i = the two block ids, lower first; the
+ * second is -1 where the block meets the padding block (a bye: nb odd only). Every step's pairs
+ * are disjoint and every unordered pair of blocks occurs in exactly one step. */
+int vr_jacobi_schedule(int64_t nb, int32_t* pairs);
+
+/* vr_plssvd_folds_f64 on the Jacobi solver: the same arguments and outputs, with every run
+ * fold's C formed at once (the arithmetic of vr_fold_xcov_f64), one batched vr_svd_jacobi_f64
+ * over the n_run folds, then per fold the first k components divided by the training standard
+ * deviation and scored as there. Differences: sigma and null come from the Jacobi solve; u and v
+ * are unit vectors on their own, so imbalance (where requested) is written as 0.0; the call
+ * synchronises with the host (vr_svd_jacobi_f64) and returns VR_ENOCONV where that does.
+ * max(p, q) <= 4096. VR_EWORKSPACE below vr_plssvd_folds_svd_workspace(p, q, k, longest test
+ * fold among those run, n_run). */
+size_t vr_plssvd_folds_svd_workspace(int64_t p, int64_t q, int64_t k, int64_t max_test, int64_t n_run);
+int vr_plssvd_folds_svd_f64(const float* X, int64_t ldx, const float* Y, int64_t ldy, int64_t p, int64_t q,
+                            const int32_t* rows, const int64_t* seg, int64_t F, int64_t n_run,
+                            const double* mean_x, const double* mean_y, const double* S, const double* stats,
+                            int64_t k, double* corr, double* cov, double* sigma, int32_t* null,
+                            double* imbalance, int64_t wfold, double* weights, double* wmean, double* wstd,
+                            void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------
  * Host: legacy numpy RandomState (MT19937) index streams, bit-exact.

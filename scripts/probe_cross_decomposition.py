@@ -17,6 +17,15 @@ into one JSON file (default profiles/cross_decomposition_probe.json) under its o
       * with `sklearn`: the same workload through scikit-learn (GaussianRandomProjection, KFold,
         PLSSVD, np.corrcoef, np.cov) on the threads the environment gives, wall clock, once; null
         when scikit-learn does not import or the step was not asked for.
+      * with `--solver jacobi` (anywhere on the command line; the default file is then
+        profiles/svd_jacobi_probe.json): the folds go through vr_plssvd_folds_svd_f64, all
+        FOLDS_RUN of them in one batched Jacobi SVD. folds_ms is then wall clock around the call
+        (it synchronises with the host once per sweep), jacobi_stage_ms the library's event
+        timers (staging, the step launches of all sweeps with the replay on R inside them,
+        finish), and one more batched vr_svd_jacobi_f64 on the same C gives sweeps_per_fold, its
+        own wall clock (svd_alone_ms) and step_launches = steps per sweep x the most sweeps.
+        status is "converged", or the library's message where a fold hit the sweep cap (the
+        times are then those of the capped run and the sweep counts are left out).
   resources   registers, scratch and LDS of the kernels of csrc/xcov.hip from the compiler's
       resource-usage remarks (needs hipcc, no device).
 
@@ -25,6 +34,9 @@ k_cov's rate for comparison is the 46.6 TF/s of DESIGN.md 3.9. The committed fil
   P="python scripts/probe_cross_decomposition.py"
   timeout -k 10 400 $P shape 1000 4096 3 1 sklearn && timeout -k 10 400 $P shape 10000 4096 3 1 sklearn \
     && timeout -k 10 400 $P shape 10000 43264 3 0 && $P resources
+and profiles/svd_jacobi_probe.json one run of
+  timeout -k 10 400 $P --solver jacobi shape 1000 4096 3 8 sklearn \
+    && timeout -k 10 400 $P --solver jacobi shape 10000 4096 3 8 sklearn
 """
 import json
 import os
@@ -89,7 +101,47 @@ def _sklearn(x, y):
             "threads": os.environ.get("OMP_NUM_THREADS")}
 
 
-def shape(out_path, n, d, reps, folds_run, with_sklearn):
+def _jacobi_folds(X, mo, k, folds_run):
+    """The folds on the Jacobi solver, and the batched SVD of the same C on its own."""
+    import torch
+
+    from visreps_amd._lib import KTIMER_SVD, ktimer_enable, ktimer_read
+
+    from visreps_amd._lib import VisrepsHipError
+
+    L = max(mo.p, mo.q)
+    b = 8 if L <= 1024 else 4 if L <= 2048 else 2
+    nb = -(-min(mo.p, mo.q) // b)
+    steps = nb + (nb & 1) - 1
+    # code objects and the LDS attribute of this block size, on a matrix of two blocks
+    X.svd_jacobi(torch.eye(2 * b, L, dtype=torch.float64, device=mo.dev))
+    torch.cuda.synchronize()
+    rec = {"solver": "jacobi", "block_rows": b, "steps_per_sweep": steps, "status": "converged"}
+    ktimer_enable(True)
+    t0 = time.perf_counter()
+    try:
+        out = mo.solve(k, folds_run, solver="jacobi")
+        rec["n_null_per_fold"] = [int(v) for v in out[3].bool().sum(dim=1).tolist()]
+    except VisrepsHipError as e:  # VR_ENOCONV: a fold still rotated in the last allowed sweep
+        rec["status"] = str(e)
+    torch.cuda.synchronize()
+    wall = (time.perf_counter() - t0) * 1e3
+    stages = {name: round(ktimer_read(name)[0], 2) for name in KTIMER_SVD}
+    ktimer_enable(False)
+    rec.update({"folds_ms": round(wall, 1), "per_fold_ms": round(wall / folds_run, 1), "jacobi_stage_ms": stages,
+                "folds_other_ms": round(wall - sum(stages.values()), 1)})
+    if rec["status"] == "converged":
+        C = mo.fold_xcov()[:folds_run].contiguous()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        sweeps = [int(v) for v in X._svd_jacobi(C)[4].tolist()]
+        torch.cuda.synchronize()
+        rec.update({"svd_alone_ms": round((time.perf_counter() - t0) * 1e3, 1), "sweeps_per_fold": sweeps,
+                    "step_launches": steps * max(sweeps)})
+    return rec
+
+
+def shape(out_path, n, d, reps, folds_run, with_sklearn, solver="eigh"):
     import torch
 
     from visreps_amd._lib import KTIMER_EIG, ktimer_enable, ktimer_read
@@ -119,7 +171,9 @@ def shape(out_path, n, d, reps, folds_run, with_sklearn):
     X._Moments(zx, zy, rows, seg)
     mo, mom_ms = _events(lambda: X._Moments(zx, zy, rows, seg), reps)
     rec_folds = {"folds_run": folds_run}
-    if folds_run > 0:
+    if folds_run > 0 and solver == "jacobi":
+        rec_folds.update(_jacobi_folds(X, mo, k, folds_run))
+    elif folds_run > 0:
         ktimer_enable(True)
         out, fold_ms = _events(lambda: mo.solve(k, folds_run), 1)
         stages = {name: round(ktimer_read(name)[0], 2) for name in KTIMER_EIG}
@@ -175,13 +229,20 @@ def resources(out_path):
 
 def main():
     args = sys.argv[1:]
-    out_path = os.path.join(ROOT, "profiles", "cross_decomposition_probe.json")
+    solver = "eigh"
+    if "--solver" in args:
+        at = args.index("--solver")
+        solver, args = args[at + 1], args[:at] + args[at + 2:]
+        if solver not in ("eigh", "jacobi"):
+            raise SystemExit(f"unknown solver {solver!r}")
+    out_path = os.path.join(ROOT, "profiles", "svd_jacobi_probe.json" if solver == "jacobi"
+                            else "cross_decomposition_probe.json")
     if args and args[0] == "--out":
         out_path, args = args[1], args[2:]
     step = args[0] if args else "shape"
     if step == "shape":
         shape(out_path, int(args[1]) if len(args) > 1 else 1000, int(args[2]) if len(args) > 2 else 4096,
-              int(args[3]) if len(args) > 3 else 3, int(args[4]) if len(args) > 4 else 1, "sklearn" in args[5:])
+              int(args[3]) if len(args) > 3 else 3, int(args[4]) if len(args) > 4 else 1, "sklearn" in args[5:], solver)
     elif step == "resources":
         resources(out_path)
     else:

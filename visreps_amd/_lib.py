@@ -277,6 +277,18 @@ _PROTOTYPES = {
         [_vp, _c_i64, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _c_i64,
          _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _c_sz, _vp],
     ),
+    "vr_svd_jacobi_workspace": (_c_sz, [_c_i64, _c_i64, _c_i64]),
+    "vr_svd_jacobi_f64": (
+        ctypes.c_int,
+        [_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp],
+    ),
+    "vr_jacobi_schedule": (ctypes.c_int, [_c_i64, _vp]),
+    "vr_plssvd_folds_svd_workspace": (_c_sz, [_c_i64, _c_i64, _c_i64, _c_i64, _c_i64]),
+    "vr_plssvd_folds_svd_f64": (
+        ctypes.c_int,
+        [_vp, _c_i64, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _c_i64,
+         _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _c_sz, _vp],
+    ),
     "vr_legacy_choice": (ctypes.c_int, [ctypes.c_uint32, _c_i64, _c_i64, _c_i64, _vp]),
     "vr_percentile_linear": (ctypes.c_double, [_vp, _c_i64, ctypes.c_double]),
 }
@@ -375,6 +387,10 @@ KTIMER_KNN = {"knn_stage": 13, "k_knn_cand": 14, "knn_rerank": 15, "k_knn_exact_
 # for vr_eigh_top_f64 the inverse iterations (stage C) and the back-transformation (stage D)
 KTIMER_EIG = {"eig_tridiag": 17, "eig_bisect": 18, "eig_invit": 19, "eig_back": 20}
 
+# the batched Jacobi SVD (csrc/svd.hip): staging, the step launches of every sweep (the replay on
+# R runs inside the step kernel), final norms + finish
+KTIMER_SVD = {"svd_stage": 21, "svd_step": 22, "svd_finish": 23}
+
 
 def ktimer_enable(on: bool = True) -> None:
     """Start (clearing the totals) or stop the library's per-launch HIP-event timing of the
@@ -387,7 +403,8 @@ def ktimer_read(kernel: str) -> tuple[float, int, float]:
     walked (engine kernels) or tile FLOPs (Gram kernels)."""
     ms, n, u = ctypes.c_double(), ctypes.c_int64(), ctypes.c_double()
     kid = (KTIMER_KERNELS[kernel] if kernel in KTIMER_KERNELS else
-           KTIMER_KNN[kernel] if kernel in KTIMER_KNN else KTIMER_EIG[kernel])
+           KTIMER_KNN[kernel] if kernel in KTIMER_KNN else
+           KTIMER_SVD[kernel] if kernel in KTIMER_SVD else KTIMER_EIG[kernel])
     check(lib().vr_ktimer_read(kid, ctypes.byref(ms), ctypes.byref(n), ctypes.byref(u)),
           "vr_ktimer_read")
     return ms.value, n.value, u.value

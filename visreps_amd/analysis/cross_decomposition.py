@@ -6,6 +6,7 @@
   fold_cross_covariances       every fold's standardised training X_s^T Y_s from one moment pass
   plssvd_fit                   PLSSVD(n_components).fit: weights, singular values, means, stds
   plssvd_cv                    per fold and component: test correlation, covariance, singular value
+  svd_jacobi                   batched thin SVD of float64 matrices (one-sided Jacobi, csrc/svd.hip)
   compute_cross_decomposition_alignment   the reference's entry point, same result dicts
 
 The reference fits PLSSVD once per fold on 7/8 of the rows. Here one pass over all rows gives
@@ -13,7 +14,9 @@ each test fold's cross-moment block S_f (fp64 MFMA, centred about the global fp6
 column statistics; fold f's training cross-covariance is the total minus S_f, re-centred and
 scaled by the training mean and ddof=1 standard deviation. Its SVD is read off the top of the
 spectrum of J = [[0, C], [C^T, 0]] with the project's own symmetric eigensolver
-(vr_eigh_top_f64): no library solve, no squared condition number.
+(vr_eigh_top_f64): no library solve, no squared condition number. That is solver="eigh", the
+default. solver="jacobi" decomposes every fold's C directly and at once with the batched
+one-sided Jacobi SVD (vr_svd_jacobi_f64), which is built for nearly all min(p, q) components.
 
 Two deliberate differences from the reference:
   * A component past the rank of C (sigma_j <= 64 (p + q) eps sigma_1) is a null-space vector
@@ -40,9 +43,18 @@ from .rsa import _device_for, _ptr
 
 __all__ = ["gaussian_random_matrix", "gaussian_random_projection", "kfold_indices", "fold_cross_covariances",
            "plssvd_fit", "plssvd_cv", "compute_cross_decomposition_alignment"]
+# svd_jacobi is public too; __all__ stays the reference module's surface
+
+SOLVERS = ("eigh", "jacobi")
 
 RESULTS_DIR = "logs/eval/cross_decomposition"
 RESULTS_FILE = RESULTS_DIR + "/plssvd_results.pkl"
+
+
+def _check_solver(solver) -> str:
+    if solver not in SOLVERS:
+        raise ValueError(f"solver must be one of {SOLVERS}: got {solver!r}")
+    return solver
 
 
 def _seed_of(seed) -> int:
@@ -178,8 +190,10 @@ class _Moments:
                                      stream_of(dev)), "vr_fold_xcov_f64")
         return C
 
-    def solve(self, k: int, n_run: int, wfold: int | None = None):
-        """vr_plssvd_folds_f64 over folds 0 .. n_run - 1."""
+    def solve(self, k: int, n_run: int, wfold: int | None = None, solver: str = "eigh"):
+        """vr_plssvd_folds_f64 (solver="eigh") or vr_plssvd_folds_svd_f64 (solver="jacobi") over
+        folds 0 .. n_run - 1."""
+        _check_solver(solver)
         p, q, F, dev, m = self.p, self.q, self.F, self.dev, self.p + self.q
         f64 = dict(dtype=torch.float64, device=dev)
         corr, cov = torch.empty((n_run, k), **f64), torch.empty((n_run, k), **f64)
@@ -190,15 +204,20 @@ class _Moments:
             W, wmean, wstd = torch.empty((k, m), **f64), torch.empty(m, **f64), torch.empty(m, **f64)
         max_test = int(np.max(np.diff(self.seg)[:n_run])) if n_run else 0
         L = lib()
-        ws = workspace.get(dev, L.vr_plssvd_folds_workspace(p, q, k, max_test), "plssvd")
+        if solver == "jacobi":
+            fn, name = L.vr_plssvd_folds_svd_f64, "vr_plssvd_folds_svd_f64"
+            ws = workspace.get(dev, L.vr_plssvd_folds_svd_workspace(p, q, k, max_test, n_run), "plssvd_svd")
+        else:
+            fn, name = L.vr_plssvd_folds_f64, "vr_plssvd_folds_f64"
+            ws = workspace.get(dev, L.vr_plssvd_folds_workspace(p, q, k, max_test), "plssvd")
         with torch.cuda.device(dev):
-            check(L.vr_plssvd_folds_f64(
+            check(fn(
                 _ptr(self.zx), int(self.zx.stride(0)), _ptr(self.zy), int(self.zy.stride(0)), p, q,
                 None if self.rows is None else _ptr(self.rows), self.seg.ctypes.data, F, n_run, _ptr(self.mean_x),
                 _ptr(self.mean_y), _ptr(self.S), _ptr(self.stats), k, _ptr(corr), _ptr(cov), _ptr(sigma),
                 _ptr(null), _ptr(imb), -1 if wfold is None else int(wfold), None if W is None else _ptr(W),
                 None if W is None else _ptr(wmean), None if W is None else _ptr(wstd), _ptr(ws), ws.numel(),
-                stream_of(dev)), "vr_plssvd_folds_f64")
+                stream_of(dev)), name)
         return corr, cov, sigma, null, imb, W, wmean, wstd
 
 
@@ -219,11 +238,54 @@ def fold_cross_covariances(Zx, Zy, folds) -> torch.Tensor:
     return _Moments(zx, zy, rows, seg).fold_xcov()
 
 
-def plssvd_fit(X, Y, n_components: int) -> dict:
+def _svd_jacobi(a: torch.Tensor):
+    """vr_svd_jacobi_f64 on a contiguous float64 (batch, p, q) device tensor: S (batch, r), the
+    rows u_j (batch, r, p), the rows v_j (batch, r, q), null (batch, r) int32 and the sweeps each
+    member ran (batch) int32."""
+    nb, p, q = (int(v) for v in a.shape)
+    dev, r = a.device, min(p, q)
+    S = torch.empty((nb, r), dtype=torch.float64, device=dev)
+    Ur = torch.empty((nb, r, p), dtype=torch.float64, device=dev)
+    Vh = torch.empty((nb, r, q), dtype=torch.float64, device=dev)
+    null = torch.empty((nb, r), dtype=torch.int32, device=dev)
+    sweeps = torch.empty(nb, dtype=torch.int32, device=dev)
+    L = lib()
+    ws = workspace.get(dev, L.vr_svd_jacobi_workspace(nb, p, q), "svd_jacobi")
+    with torch.cuda.device(dev):
+        check(L.vr_svd_jacobi_f64(_ptr(a), nb, p, q, q, p * q, _ptr(S), _ptr(Ur), _ptr(Vh), _ptr(null),
+                                  _ptr(sweeps), _ptr(ws), ws.numel(), stream_of(dev)), "vr_svd_jacobi_f64")
+    return S, Ur, Vh, null, sweeps
+
+
+def svd_jacobi(A):
+    """Thin SVD of a float64 matrix (p, q) or batch of matrices (batch, p, q) by one-sided Jacobi
+    (vr_svd_jacobi_f64), max(p, q) <= 4096. Returns (U, S, Vh, null) shaped like
+    torch.linalg.svd(A, full_matrices=False), on A's device (a CPU tensor or numpy array is moved
+    to the current HIP device): U (.., p, r), S (.., r) descending, Vh (.., r, q), r = min(p, q),
+    and bool null (.., r), True where sigma_j <= 64 (p + q) eps sigma_1: both vectors of such a
+    component are NaN. Column j of U has its largest-magnitude entry positive (svd_flip's u-based
+    rule). A member with a non-finite entry gives NaN and null everywhere; the others are
+    unaffected. Deterministic; a member's result does not depend on its batch."""
+    if not isinstance(A, torch.Tensor):
+        A = torch.as_tensor(np.asarray(A))
+    if A.dtype != torch.float64:
+        raise TypeError(f"A must be float64: got {A.dtype} (cast it; there is no float32 path)")
+    if A.ndim not in (2, 3) or min(A.shape) < 1:
+        raise ValueError(f"A must be a non-empty 2-D or 3-D (batch x rows x columns) array: got shape "
+                         f"{tuple(A.shape)}")
+    a = A.to(_device_for(A))
+    S, Ur, Vh, null, _ = _svd_jacobi((a if A.ndim == 3 else a.unsqueeze(0)).contiguous())
+    U, null = Ur.transpose(1, 2).contiguous(), null.bool()
+    return (U, S, Vh, null) if A.ndim == 3 else (U[0], S[0], Vh[0], null[0])
+
+
+def plssvd_fit(X, Y, n_components: int, solver: str = "eigh") -> dict:
     """PLSSVD(n_components).fit(X, Y) on float32 X (n, p), Y (n, q): the one-segment case of the
     fold solver (every row trains). Returns float64 numpy arrays x_weights (p, k), y_weights (q, k),
     singular_values (k), x_mean, y_mean, x_std, y_std, and the bool null flags (k); a null
-    component's weights are NaN."""
+    component's weights are NaN. solver: "eigh" (the eigensolver on J) or "jacobi" (the direct
+    Jacobi SVD of C, max(p, q) <= 4096)."""
+    _check_solver(solver)
     zx, zy = _rows_f32(X, "X"), _rows_f32(Y, "Y")
     n, k = int(zx.size(0)), int(n_components)
     if n < 2:
@@ -231,7 +293,7 @@ def plssvd_fit(X, Y, n_components: int) -> dict:
     if not 1 <= k <= min(zx.size(1), zy.size(1)):
         raise ValueError(f"n_components={k} must be between 1 and min(p, q) = {min(zx.size(1), zy.size(1))}")
     mo = _Moments(zx, zy, None, np.array([0, 0, n], dtype=np.int64))  # fold 0 tests nothing
-    _, _, sigma, null, _, W, wmean, wstd = mo.solve(k, 1, wfold=0)
+    _, _, sigma, null, _, W, wmean, wstd = mo.solve(k, 1, wfold=0, solver=solver)
     p = mo.p
     W, wmean, wstd = W.cpu().numpy(), wmean.cpu().numpy(), wstd.cpu().numpy()
     return {"x_weights": W[:, :p].T.copy(), "y_weights": W[:, p:].T.copy(),
@@ -239,12 +301,15 @@ def plssvd_fit(X, Y, n_components: int) -> dict:
             "x_mean": wmean[:p], "y_mean": wmean[p:], "x_std": wstd[:p], "y_std": wstd[p:]}
 
 
-def plssvd_cv(Zx, Zy, n_folds: int = 8, seed=None, n_components: int | None = None) -> dict:
+def plssvd_cv(Zx, Zy, n_folds: int = 8, seed=None, n_components: int | None = None,
+              solver: str = "eigh") -> dict:
     """Shuffled n_folds-fold PLS-SVD of float32 Zx (n, p), Zy (n, q). Returns float64 numpy arrays
     correlations, covariances, singular_values (n_folds, k), bool null (n_folds, k), the
     half-norm imbalance |2 |u|^2 - 1| (n_folds, k) and n_components = k, which defaults to
     min(first fold's training size, p, q) as the reference. Null components and test folds of one
-    row give NaN."""
+    row give NaN. solver="jacobi" solves all folds in one batched Jacobi SVD (max(p, q) <= 4096);
+    its u and v are unit vectors on their own, so its imbalance is 0."""
+    _check_solver(solver)
     zx, zy = _rows_f32(Zx, "Zx"), _rows_f32(Zy, "Zy")
     n = int(zx.size(0))
     folds = kfold_indices(n, n_folds, seed)
@@ -255,7 +320,7 @@ def plssvd_cv(Zx, Zy, n_folds: int = 8, seed=None, n_components: int | None = No
     if not 1 <= k <= lim:
         raise ValueError(f"n_components={k} must be between 1 and min(p, q) = {lim}")
     mo = _Moments(zx, zy, rows, seg)
-    corr, cov, sigma, null, imb, _, _, _ = mo.solve(k, mo.F)
+    corr, cov, sigma, null, imb, _, _, _ = mo.solve(k, mo.F, solver=solver)
     return {"correlations": corr.cpu().numpy(), "covariances": cov.cpu().numpy(),
             "singular_values": sigma.cpu().numpy(), "null": null.cpu().numpy().astype(bool),
             "imbalance": imb.cpu().numpy(), "n_components": k}
@@ -268,7 +333,10 @@ def compute_cross_decomposition_alignment(cfg, activations_dict, neural_data, n_
     n_folds-fold PLS-SVD gives per-component test correlation and covariance, averaged over folds.
     One result dict per layer, the reference's keys plus n_valid_components (components that are
     not null in any fold; past them the means are NaN); appended to
-    logs/eval/cross_decomposition/plssvd_results.pkl under the working directory."""
+    logs/eval/cross_decomposition/plssvd_results.pkl under the working directory. The solver is
+    cfg's "solver" entry ("eigh" where it has none), as plssvd_cv's; the signature is the
+    reference's."""
+    solver = _check_solver(cfg.get("solver", "eigh"))
     os.makedirs(RESULTS_DIR, exist_ok=True)
     if os.path.exists(RESULTS_FILE):
         with open(RESULTS_FILE, "rb") as f:
@@ -290,7 +358,7 @@ def compute_cross_decomposition_alignment(cfg, activations_dict, neural_data, n_
         if activations.ndim > 2:
             activations = activations.flatten(start_dim=1)
         projected = gaussian_random_projection(activations, n_projection, seed)
-        cv = plssvd_cv(projected, neural, n_folds=n_folds, seed=seed)
+        cv = plssvd_cv(projected, neural, n_folds=n_folds, seed=seed, solver=solver)
         results.append({
             "layer": layer_name,
             "analysis": "cross_decomposition",

@@ -137,7 +137,10 @@ enum KtKernel : int {
   KT_EIG_BISECT = 18,   // eigvals.hip stage B: bounds + bisection (units: Sturm terms)
   KT_EIG_INVIT = 19,    // eigvals.hip stage C: shifts, start, inverse iterations + Gram-Schmidt (units: solve steps)
   KT_EIG_BACK = 20,     // eigvals.hip stage D: k_eigv_back (units: bytes of reflectors read)
-  KT_N = 21
+  KT_SVD_STAGE = 21,    // svd.hip: transpose staging, R = I, the first row norms, setup (units: bytes moved)
+  KT_SVD_STEP = 22,     // svd.hip: the k_svd_step launches of one sweep, R replay included (units: 3 n^2 L FLOPs per member)
+  KT_SVD_FINISH = 23,   // svd.hip: final row norms + k_svd_finish (units: bytes moved)
+  KT_N = 24
 };
 bool ktimer_on();
 struct KtScope {

@@ -26,6 +26,9 @@
 //                  values are exact in fp64, the sum is rounded once to fp32) and the test scores.
 // k_svd_extract    u, v from the eigenvector rows: halves normalised, svd_flip's u-based sign,
 //                  divided by the training standard deviation; null components flagged.
+// k_svd_weights    the same outputs from the unit rows of vr_svd_jacobi_f64 (svd.hip), for
+//                  vr_plssvd_folds_svd_f64: C of every run fold at once (k_fold_xcov), one batched
+//                  Jacobi SVD, then the scores as above.
 // k_col_corr_cov   Pearson r and ddof=1 covariance of paired score columns, two passes.
 // Roofline: fp64 MFMA. Algorithmic FLOPs: k_xcov 2 n p q, k_xgemm_nt 2 M N K.
 #include <algorithm>
@@ -630,6 +633,65 @@ static int64_t seg_max(const int64_t* seg, int64_t F) {
   return mx;
 }
 
+// The Jacobi path's k_svd_extract: component j of one fold from vr_svd_jacobi_f64's unit rows
+// U [r][p], Vt [r][q] (sign and NaN fill already applied there). One workgroup per component.
+//   Wu [k][m] (nullable)  u then v;  Wp [k][m]  the same divided by the training standard deviations
+__global__ __launch_bounds__(256) void k_svd_weights(const double* __restrict__ U, const double* __restrict__ Vt,
+                                                     const double* __restrict__ S, const int32_t* __restrict__ nl,
+                                                     int64_t p, int64_t q, const double* __restrict__ trs,
+                                                     double* __restrict__ Wu, double* __restrict__ Wp,
+                                                     double* __restrict__ sigma, int32_t* __restrict__ null,
+                                                     double* __restrict__ imb) {
+  const int64_t j = blockIdx.x, m = p + q;
+  for (int64_t i = threadIdx.x; i < m; i += 256) {
+    const double unit = i < p ? U[j * p + i] : Vt[j * q + (i - p)];
+    if (Wu != nullptr) Wu[j * m + i] = unit;
+    Wp[j * m + i] = unit / trs[i];
+  }
+  if (threadIdx.x == 0) {
+    sigma[j] = S[j];
+    null[j] = nl[j];
+    if (imb != nullptr) imb[j] = 0.0;
+  }
+}
+
+struct FoldsSvdLayout {
+  double *T, *trm, *trs, *trabs, *C, *Sv, *U, *Vt, *Wp, *SX, *SY;
+  int32_t *nl, *sweeps;
+  void* svd;
+  size_t svd_bytes;
+  void* gemm;
+  size_t gemm_bytes;
+  size_t bytes;
+};
+
+static FoldsSvdLayout folds_svd_layout(void* ws, int64_t p, int64_t q, int64_t k, int64_t max_test, int64_t n_run) {
+  FoldsSvdLayout L;
+  const int64_t m = p + q, r = std::min(p, q), nr = std::max<int64_t>(n_run, 1), kk = std::max<int64_t>(k, 1);
+  Carver c(ws);
+  L.T = c.take<double>((size_t)(p * q));
+  L.trm = c.take<double>((size_t)(nr * m));
+  L.trs = c.take<double>((size_t)(nr * m));
+  L.trabs = c.take<double>((size_t)(nr * m));
+  L.C = c.take<double>((size_t)(nr * p * q));
+  L.Sv = c.take<double>((size_t)(nr * r));
+  L.U = c.take<double>((size_t)(nr * r * p));
+  L.Vt = c.take<double>((size_t)(nr * r * q));
+  L.nl = c.take<int32_t>((size_t)(nr * r));
+  L.sweeps = c.take<int32_t>((size_t)nr);
+  L.Wp = c.take<double>((size_t)(kk * m));
+  L.SX = c.take<double>((size_t)(std::max<int64_t>(max_test, 1) * kk));
+  L.SY = c.take<double>((size_t)(std::max<int64_t>(max_test, 1) * kk));
+  L.svd_bytes = vr_svd_jacobi_workspace(nr, p, q);
+  L.svd = c.take<char>(L.svd_bytes);
+  // as folds_layout: a score product's partial tiles number at most 4 CUs + ntile
+  const int64_t tmax = ((std::max<int64_t>(max_test, 1) + XT - 1) / XT) * ((kk + XT - 1) / XT);
+  L.gemm_bytes = (size_t)(4LL * num_cus() + tmax) * XT * XT * sizeof(double) + 256;
+  L.gemm = c.take<char>(L.gemm_bytes);
+  L.bytes = c.bytes();
+  return L;
+}
+
 }  // namespace vr
 
 using namespace vr;
@@ -821,6 +883,79 @@ int vr_plssvd_folds_f64(const float* X, int64_t ldx, const float* Y, int64_t ldy
     VR_TRY(vr_eigh_top_f64(L.J, m, m, k, L.w, L.V, m, L.eig, L.eig_bytes, stream));
     k_svd_extract<<<(unsigned)k, 256, 0, st>>>(L.w, L.V, m, p, q, trs, keep ? weights : nullptr, L.Wp,
                                                sigma + f * k, null + f * k,
+                                               imbalance != nullptr ? imbalance + f * k : nullptr);
+    VR_CHECK_LAUNCH();
+    if (nt > 0) {  // scores of the test rows: (z - training mean) . u / s
+      const int32_t* tr = rows != nullptr ? rows + seg[f] : nullptr;
+      const float* Xt = rows != nullptr ? X : X + seg[f] * ldx;
+      const float* Yt = rows != nullptr ? Y : Y + seg[f] * ldy;
+      VR_TRY((xgemm_launch<double, double>(Xt, nt, p, ldx, tr, trabs, L.Wp, k, m, L.SX, k, L.gemm, st)));
+      VR_TRY((xgemm_launch<double, double>(Yt, nt, q, ldy, tr, trabs + p, L.Wp + p, k, m, L.SY, k, L.gemm, st)));
+    }
+    k_col_corr_cov<<<(unsigned)((k + 255) / 256), 256, 0, st>>>(L.SX, L.SY, nt, k, k, corr + f * k, cov + f * k);
+    VR_CHECK_LAUNCH();
+  }
+  return VR_OK;
+}
+
+size_t vr_plssvd_folds_svd_workspace(int64_t p, int64_t q, int64_t k, int64_t max_test, int64_t n_run) {
+  if (p <= 0 || q <= 0 || k < 0 || max_test < 0 || n_run < 0) return 256;
+  return folds_svd_layout(nullptr, p, q, k, max_test, n_run).bytes;
+}
+
+int vr_plssvd_folds_svd_f64(const float* X, int64_t ldx, const float* Y, int64_t ldy, int64_t p, int64_t q,
+                            const int32_t* rows, const int64_t* seg, int64_t F, int64_t n_run,
+                            const double* mean_x, const double* mean_y, const double* S, const double* stats,
+                            int64_t k, double* corr, double* cov, double* sigma, int32_t* null,
+                            double* imbalance, int64_t wfold, double* weights, double* wmean, double* wstd,
+                            void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  VR_REQUIRE(p >= 1 && q >= 1 && ldx >= p && ldy >= q && std::max(p, q) <= 4096,
+             "vr_plssvd_folds_svd_f64: bad shape p=%lld q=%lld (max(p, q) <= 4096)", (long long)p, (long long)q);
+  VR_REQUIRE(seg_ok(seg, F) && F <= INT32_MAX && n_run >= 0 && n_run <= F && n_run <= 65535,
+             "vr_plssvd_folds_svd_f64: bad segments");
+  VR_REQUIRE(k >= 1 && k <= std::min(p, q), "vr_plssvd_folds_svd_f64: k=%lld outside [1, min(p, q)]", (long long)k);
+  VR_REQUIRE(X != nullptr && Y != nullptr && S != nullptr && stats != nullptr && mean_x != nullptr &&
+                 mean_y != nullptr && corr != nullptr && cov != nullptr && sigma != nullptr && null != nullptr,
+             "vr_plssvd_folds_svd_f64: null pointer");
+  VR_REQUIRE(weights == nullptr || (wfold >= 0 && wfold < n_run && wmean != nullptr && wstd != nullptr),
+             "vr_plssvd_folds_svd_f64: bad weights request");
+  int64_t max_test = 0;
+  for (int64_t f = 0; f < n_run; ++f) {
+    VR_REQUIRE(seg[F] - (seg[f + 1] - seg[f]) >= 2,
+               "vr_plssvd_folds_svd_f64: fold %lld leaves fewer than 2 training rows", (long long)f);
+    max_test = std::max(max_test, seg[f + 1] - seg[f]);
+  }
+  if (ws == nullptr || ws_bytes < vr_plssvd_folds_svd_workspace(p, q, k, max_test, n_run)) {
+    set_error("vr_plssvd_folds_svd_f64: workspace too small");
+    return VR_EWORKSPACE;
+  }
+  if (n_run == 0) return VR_OK;
+  hipStream_t st = as_stream(stream);
+  const int64_t m = p + q, pq = p * q, r = std::min(p, q);
+  const FoldsSvdLayout L = folds_svd_layout(ws, p, q, k, max_test, n_run);
+  k_seg_total<<<(unsigned)((pq + 255) / 256), 256, 0, st>>>(S, (int)F, pq, L.T);
+  VR_CHECK_LAUNCH();
+  // every run fold's statistics and C, then all their SVDs in one batch
+  for (int64_t f = 0; f < n_run; ++f) {
+    const double n_tr = (double)(seg[F] - (seg[f + 1] - seg[f]));
+    const bool keep = weights != nullptr && f == wfold;
+    double* trs = keep ? wstd : L.trs + f * m;
+    k_fold_stats<<<(unsigned)((m + 255) / 256), 256, 0, st>>>(stats, (int)F, m, (int)f, n_tr, mean_x, mean_y, p,
+                                                            L.trm + f * m, trs, keep ? wmean : L.trabs + f * m);
+    VR_CHECK_LAUNCH();
+    k_fold_xcov<<<(unsigned)((pq + 255) / 256), 256, 0, st>>>(L.T, S + f * pq, L.trm + f * m, trs, n_tr, p, q,
+                                                            L.C + f * pq);
+    VR_CHECK_LAUNCH();
+  }
+  VR_TRY(vr_svd_jacobi_f64(L.C, n_run, p, q, q, pq, L.Sv, L.U, L.Vt, L.nl, L.sweeps, L.svd, L.svd_bytes, stream));
+  for (int64_t f = 0; f < n_run; ++f) {
+    const int64_t nt = seg[f + 1] - seg[f];
+    const bool keep = weights != nullptr && f == wfold;
+    const double* trs = keep ? wstd : L.trs + f * m;
+    const double* trabs = keep ? wmean : L.trabs + f * m;
+    k_svd_weights<<<(unsigned)k, 256, 0, st>>>(L.U + f * r * p, L.Vt + f * r * q, L.Sv + f * r, L.nl + f * r, p, q,
+                                               trs, keep ? weights : nullptr, L.Wp, sigma + f * k, null + f * k,
                                                imbalance != nullptr ? imbalance + f * k : nullptr);
     VR_CHECK_LAUNCH();
     if (nt > 0) {  // scores of the test rows: (z - training mean) . u / s
