@@ -14,22 +14,19 @@
 // the shifts are the means of the finite entries of the whole matrices rounded to float32 (0 if
 // that is not finite), so x and y are exact in fp64 and only condition the sums.
 //
-// k_cka_shift_rows   per-row sums of the finite entries (the shift's numerator; pboot_shift
-//             of pearson_boot.hip divides and rounds).
-// k_ckaboot   the tiling of k_pboot: a workgroup owns 64 rows i x 64 subsets, wave w rows
-//             16 w .. 16 w + 15 against four 16-subset blocks of v_mfma_f64_16x16x4_f64, the W
-//             panel (pboot_build_w) widened to 0.0 / 1.0 in double-buffered LDS, K and L read
-//             straight from global memory, one float4 per lane and panel. The walk differs: all
-//             column panels 0 .. n, no j > i mask (u and v need the whole row, and the product
-//             forms take the diagonal and both triangles). Six quantities per (row, subset):
-//             sum_j w_j {x, y, x^2, y^2, x y, non-finite}; 6 x 4 accumulators of 4 doubles per
-//             lane (192 registers, one wave per SIMD). A non-finite entry of K or L is staged
-//             as 0 in both and counted: a subset scores NaN iff some (i, j) with i and j in it,
-//             the diagonal included, is non-finite.
-//             Epilogue (C/D: col = lane & 15, row = (lane >> 4) + 4 reg): for a row i in the
-//             subset, u = acc x, v = acc y; nine partials u, v, u v, u^2, v^2, sum x^2,
-//             sum y^2, sum x y, count are added over the 64 rows in a fixed order, one fp64
-//             partial per (row tile, quantity, subset).
+// The masked GEMM itself (tiling, W staging, the six staged quantities, the fixed-order tail),
+// the W kernels, the shift's division and the host driver are subset_gemm.h / pearson_boot.hip,
+// shared with the Pearson engine.
+//
+// k_cka_shift_rows   per-row sums of the finite entries (the shift's numerator).
+// k_ckaboot   subset_gemm.h's full walk: all column panels 0 .. n, no j > i mask (u and v need
+//             the whole row, and the product forms take the diagonal and both triangles). Six
+//             quantities per (row, subset): sum_j w_j {x, y, x^2, y^2, x y, non-finite}. A
+//             non-finite entry of K or L is counted: a subset scores NaN iff some (i, j) with i
+//             and j in it, the diagonal included, is non-finite.
+//             Epilogue: for a row i in the subset, u = acc x, v = acc y; nine partials u, v,
+//             u v, u^2, v^2, sum x^2, sum y^2, sum x y, count; the tail adds them over the 64
+//             rows in a fixed order, one fp64 partial per (row tile, quantity, subset).
 // k_ckaboot_reduce   adds the row tiles in tile order, forms the traces and the score (not
 //             clamped: the reference's is not) or the recompute flag. No floating-point
 //             atomics anywhere: scores are bit-identical run to run.
@@ -67,36 +64,11 @@
 #include <cmath>
 #include <vector>
 
-#include "internal.h"
+#include "subset_gemm.h"
 
 namespace vr {
 
-typedef double cf64x4 __attribute__((ext_vector_type(4)));
-typedef float cf32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int CB_T = 64;     // rows per workgroup, and subsets per workgroup
-constexpr int CB_K = 16;     // columns j per panel
-constexpr int CB_WLD = 68;   // LDS pitch of a W panel row (doubles): rows 4 apart fall 32 banks apart
-constexpr int CB_Q = 6;      // x, y, x^2, y^2, x y, non-finite count
 constexpr int CB_P = 9;      // u, v, u v, u^2, v^2, sum x^2, sum y^2, sum x y, count
-constexpr int CB_THREADS = 256;
-
-__device__ inline bool cb_finite(float f) { return (__float_as_uint(f) & 0x7f800000u) != 0x7f800000u; }
-
-// block sum of Q values per thread, 256 threads: wave shuffle tree, then the four waves in order
-template <int Q>
-__device__ inline void cb_block_sum(const double (&v)[Q], double (*red)[4], double (&out)[Q]) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int q = 0; q < Q; ++q) {
-    double t = v[q];
-    for (int o = 32; o > 0; o >>= 1) t += __shfl_down(t, o, 64);
-    if (lane == 0) red[q][w] = t;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < Q; ++q) out[q] = (red[q][0] + red[q][1]) + (red[q][2] + red[q][3]);
-}
 
 // per-row sums of the finite entries of the whole rows: part[2 a + {0, 1}]
 __global__ __launch_bounds__(256) void k_cka_shift_rows(const float* __restrict__ K, const float* __restrict__ L,
@@ -106,148 +78,47 @@ __global__ __launch_bounds__(256) void k_cka_shift_rows(const float* __restrict_
   double v[2] = {0.0, 0.0}, s[2];
   for (int64_t b = threadIdx.x; b < n; b += 256) {
     const float x = K[a * ld + b], y = L[a * ld + b];
-    if (cb_finite(x)) v[0] += (double)x;
-    if (cb_finite(y)) v[1] += (double)y;
+    if (finite_f32(x)) v[0] += (double)x;
+    if (finite_f32(y)) v[1] += (double)y;
   }
-  cb_block_sum<2>(v, red, s);
+  block_sum<2, true>(v, red, s);
   if (threadIdx.x < 2) part[a * 2 + threadIdx.x] = s[threadIdx.x];
 }
 
-struct CbParams {
-  const float* K;
-  const float* L;
-  int64_t n, ld;
-  const uint8_t* W;  // n_pad x s_pad bytes
-  int64_t s_pad;
-  const double* shift;
-  double* partial;  // [T][CB_P][s_pad]
-  int ST;           // subset tiles
-  bool vec;         // 16-B aligned rows: float4 loads
-};
-
-__global__ __launch_bounds__(CB_THREADS) void k_ckaboot(CbParams P) {
-  __shared__ __attribute__((aligned(16))) double Ws[2][CB_K * CB_WLD];
-  __shared__ double red[4][CB_P][CB_T];
+__global__ __launch_bounds__(SG_THREADS) void k_ckaboot(SubsetParams P) {
+  __shared__ __attribute__((aligned(16))) double Ws[2][SG_K * SG_WLD];
+  __shared__ double red[4][CB_P][SG_T];
   const int bi = blockIdx.x / P.ST, bs = blockIdx.x % P.ST;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int fm = lane & 15, fk = lane >> 4;
-  const int64_t n = P.n;
-  const int64_t i0 = (int64_t)bi * CB_T, s0 = (int64_t)bs * CB_T;
-  const int64_t i = i0 + wid * 16 + fm;  // the row this lane supplies to the A operand
-  const bool iin = i < n;
-  const float* rk = P.K + (iin ? i : 0) * P.ld;
-  const float* rl = P.L + (iin ? i : 0) * P.ld;
-  const double ck = P.shift[0], cl = P.shift[1];
-  const int np = (int)((n + CB_K - 1) / CB_K);  // >= 1; 16 np <= n_pad rows of W exist
+  const int64_t i0 = (int64_t)bi * SG_T, s0 = (int64_t)bs * SG_T;
+  f64x4 acc[SG_Q][4];
+  subset_walk<false>(P, Ws, i0, s0, wid, fm, fk, acc);
 
-  cf64x4 acc[CB_Q][4];
-#pragma unroll
-  for (int q = 0; q < CB_Q; ++q)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[q][b] = cf64x4{0.0, 0.0, 0.0, 0.0};
-
-  // this lane's 4 consecutive columns of a panel: j0 + 4 fk + e (entries outside [0, n) are 0)
-  auto load_kl = [&](int64_t j0, cf32x4& va, cf32x4& vb) {
-    const int64_t j = j0 + fk * 4;
-    va = cf32x4{0.f, 0.f, 0.f, 0.f};
-    vb = va;
-    if (!iin || j >= n) return;
-    if (P.vec && j + 4 <= n) {
-      va = *reinterpret_cast<const cf32x4*>(rk + j);
-      vb = *reinterpret_cast<const cf32x4*>(rl + j);
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        va[e] = (j + e < n) ? rk[j + e] : 0.f;
-        vb[e] = (j + e < n) ? rl[j + e] : 0.f;
-      }
-    }
-  };
-  // W panel: thread t stages row t >> 4, subsets 4 (t & 15) .. + 3
-  const int wr = threadIdx.x >> 4, wc = (threadIdx.x & 15) * 4;
-  auto load_w = [&](int64_t j0) {
-    return *reinterpret_cast<const uint32_t*>(P.W + (j0 + wr) * P.s_pad + s0 + wc);
-  };
-  auto store_w = [&](double* dst, uint32_t w) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) dst[wr * CB_WLD + wc + e] = (double)((w >> (8 * e)) & 0xffu);
-  };
-
-  cf32x4 va, vb, na, nb;
-  load_kl(0, va, vb);
-  store_w(Ws[0], load_w(0));
-  __syncthreads();
-  for (int p = 0; p < np; ++p) {
-    const int cur = p & 1;
-    const int64_t j0 = (int64_t)p * CB_K;
-    const bool more = p + 1 < np;
-    uint32_t nw = 0;
-    if (more) {
-      load_kl(j0 + CB_K, na, nb);
-      nw = load_w(j0 + CB_K);
-    }
-    const double* Wp = Ws[cur];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      // K position (fk, e) of this step is column j0 + 4 fk + e for both operands
-      const int64_t j = j0 + fk * 4 + e;
-      const float a = va[e], b = vb[e];
-      const bool in = iin && j < n;
-      const bool fin = cb_finite(a) && cb_finite(b);
-      const bool use = in && fin;
-      const double x = use ? (double)a - ck : 0.0;
-      const double y = use ? (double)b - cl : 0.0;
-      const double qv[CB_Q] = {x, y, x * x, y * y, x * y, (in && !fin) ? 1.0 : 0.0};
-#pragma unroll
-      for (int sb = 0; sb < 4; ++sb) {
-        const double w = Wp[(fk * 4 + e) * CB_WLD + sb * 16 + fm];
-#pragma unroll
-        for (int q = 0; q < CB_Q; ++q)
-          acc[q][sb] = __builtin_amdgcn_mfma_f64_16x16x4f64(qv[q], w, acc[q][sb], 0, 0, 0);
-      }
-    }
-    if (more) {
-      store_w(Ws[cur ^ 1], nw);
-      va = na;
-      vb = nb;
-    }
-    __syncthreads();
-  }
-
-  // C/D of the f64 MFMA: col (subset) = lane & 15, row = (lane >> 4) + 4 r. Keep the rows that
-  // are in the subset, form their nine partials, add the wave's 16 rows, then the four waves.
+  // the nine partials of the rows that are in the subset
+  double t[4][CB_P];
 #pragma unroll
   for (int sb = 0; sb < 4; ++sb) {
-    double t[CB_P] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int q = 0; q < CB_P; ++q) t[sb][q] = 0.0;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int64_t row = i0 + wid * 16 + fk + 4 * r;  // < n_pad
       if (P.W[row * P.s_pad + s0 + sb * 16 + fm] != 0) {
         const double u = acc[0][sb][r], v = acc[1][sb][r];
-        t[0] += u;
-        t[1] += v;
-        t[2] += u * v;
-        t[3] += u * u;
-        t[4] += v * v;
-        t[5] += acc[2][sb][r];
-        t[6] += acc[3][sb][r];
-        t[7] += acc[4][sb][r];
-        t[8] += acc[5][sb][r];
+        t[sb][0] += u;
+        t[sb][1] += v;
+        t[sb][2] += u * v;
+        t[sb][3] += u * u;
+        t[sb][4] += v * v;
+        t[sb][5] += acc[2][sb][r];
+        t[sb][6] += acc[3][sb][r];
+        t[sb][7] += acc[4][sb][r];
+        t[sb][8] += acc[5][sb][r];
       }
     }
-#pragma unroll
-    for (int q = 0; q < CB_P; ++q) {
-      double z = t[q];
-      z += __shfl_xor(z, 16, 64);
-      z += __shfl_xor(z, 32, 64);
-      if (fk == 0) red[wid][q][sb * 16 + fm] = z;
-    }
   }
-  __syncthreads();
-  for (int e = threadIdx.x; e < CB_P * CB_T; e += CB_THREADS) {
-    const int q = e / CB_T, s = e % CB_T;
-    P.partial[((int64_t)bi * CB_P + q) * P.s_pad + s0 + s] = (red[0][q][s] + red[1][q][s]) + (red[2][q][s] + red[3][q][s]);
-  }
+  subset_tail<CB_P>(P, red, bi, s0, wid, fm, fk, t);
 }
 
 // one thread per subset: row tiles added in tile order, then the score or the recompute flag
@@ -282,11 +153,6 @@ __global__ __launch_bounds__(256) void k_ckaboot_reduce(const double* __restrict
   flags[s] = flag;
 }
 
-__global__ void k_ckaboot_nan(double* __restrict__ scores, int64_t total) {
-  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (s < total) scores[s] = __builtin_nan("");
-}
-
 // ---- two-pass form ----------------------------------------------------------------------
 // SUB: row a and column b are positions in idx (k of them, n = k). rs[2 a + {0, 1}] = row sums.
 template <bool SUB>
@@ -302,7 +168,7 @@ __global__ __launch_bounds__(256) void k_cka_rowsum(const float* __restrict__ K,
     v[0] += (double)K[at];
     v[1] += (double)L[at];
   }
-  cb_block_sum<2>(v, red, s);
+  block_sum<2, true>(v, red, s);
   if (threadIdx.x < 2) rs[a * 2 + threadIdx.x] = s[threadIdx.x];
 }
 
@@ -318,7 +184,7 @@ __global__ __launch_bounds__(256) void k_cka_means(double* __restrict__ rs, int6
     v[0] += m0;
     v[1] += m1;
   }
-  cb_block_sum<2>(v, red, s);
+  block_sum<2, true>(v, red, s);
   if (threadIdx.x < 2) mu[threadIdx.x] = s[threadIdx.x] / k;
 }
 
@@ -341,7 +207,7 @@ __global__ __launch_bounds__(256) void k_cka_centred(const float* __restrict__ K
     v[1] += dx * dx;
     v[2] += dy * dy;
   }
-  cb_block_sum<3>(v, red, s);
+  block_sum<3, true>(v, red, s);
   if (threadIdx.x < 3) p3[a * 3 + threadIdx.x] = s[threadIdx.x];
 }
 
@@ -352,7 +218,7 @@ __global__ __launch_bounds__(256) void k_cka_final(const double* __restrict__ p3
   for (int64_t a = threadIdx.x; a < n; a += 256)
 #pragma unroll
     for (int q = 0; q < 3; ++q) v[q] += p3[a * 3 + q];
-  cb_block_sum<3>(v, red, s);
+  block_sum<3, true>(v, red, s);
   if (threadIdx.x == 0) {
     // an exactly zero centred sub-matrix or non-finite input: undefined, as the reference's 0 / 0
     const bool ok = n >= 2 && s[1] > 0 && s[2] > 0;
@@ -387,37 +253,6 @@ int cka_two_pass(const float* K, const float* L, int64_t n_or_k, int64_t ld, con
   return VR_OK;
 }
 
-struct CbLayout {
-  int64_t n_pad, s_pad;
-  int T, ST;
-  uint8_t* W;
-  double* partial;
-  double* part;
-  double* mu;
-  double* shift;
-  int32_t* flags;
-  size_t bytes;
-};
-
-// total: subsets including the full set
-static CbLayout cb_layout(void* ws, int64_t n, int64_t total) {
-  CbLayout L;
-  const int64_t nn = std::max<int64_t>(n, 1), tt = std::max<int64_t>(total, 1);
-  L.n_pad = (nn + CB_T - 1) / CB_T * CB_T;
-  L.s_pad = (tt + CB_T - 1) / CB_T * CB_T;
-  L.T = (int)(L.n_pad / CB_T);
-  L.ST = (int)(L.s_pad / CB_T);
-  Carver c(ws);
-  L.W = c.take<uint8_t>((size_t)L.n_pad * L.s_pad);
-  L.partial = c.take<double>((size_t)L.T * CB_P * L.s_pad);
-  L.part = c.take<double>((size_t)nn * 5);
-  L.mu = c.take<double>(2);
-  L.shift = c.take<double>(2);
-  L.flags = c.take<int32_t>((size_t)L.s_pad);
-  L.bytes = c.bytes();
-  return L;
-}
-
 static size_t cka_subset_ws(int64_t k, double** part, double** mu, void* ws) {
   Carver c(ws);
   double* p = c.take<double>((size_t)std::max<int64_t>(k, 1) * 5);
@@ -427,6 +262,31 @@ static size_t cka_subset_ws(int64_t k, double** part, double** mu, void* ws) {
   return c.bytes();
 }
 
+static const SubsetEngine CKA_BOOT = {
+    "vr_bootstrap_cka_f32",
+    CB_P,
+    [](const float* K, const float* L, int64_t n, int64_t ld, double* part, hipStream_t st) -> int {
+      k_cka_shift_rows<<<(unsigned)n, 256, 0, st>>>(K, L, n, ld, part);
+      VR_CHECK_LAUNCH();
+      return VR_OK;
+    },
+    [](int64_t n) { return (double)n * (double)n; },
+    [](const SubsetParams& P, int T, hipStream_t st) -> int {
+      k_ckaboot<<<(unsigned)(T * P.ST), SG_THREADS, 0, st>>>(P);
+      VR_CHECK_LAUNCH();
+      return VR_OK;
+    },
+    [](const SubsetLayout& Y, int64_t n, int64_t k, int64_t total, int full_first, double* scores,
+       hipStream_t st) -> int {
+      k_ckaboot_reduce<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(
+          Y.partial, Y.T, Y.s_pad, total, full_first, (double)n, (double)k, Y.shift, scores, Y.flags);
+      VR_CHECK_LAUNCH();
+      return VR_OK;
+    },
+    [](const float* K, const float* L, int64_t n_or_k, int64_t ld, const int32_t* idx, double* out, double* part,
+       double* mu, hipStream_t st) -> int { return cka_two_pass(K, L, n_or_k, ld, idx, out, 1, part, mu, st); },
+};
+
 }  // namespace vr
 
 using namespace vr;
@@ -434,65 +294,12 @@ using namespace vr;
 extern "C" {
 
 size_t vr_bootstrap_cka_workspace(int64_t n, int64_t n_sets) {
-  return cb_layout(nullptr, n, std::max<int64_t>(n_sets, 0) + 1).bytes;
+  return subset_layout(nullptr, n, std::max<int64_t>(n_sets, 0) + 1, CKA_BOOT.np).bytes;
 }
 
 int vr_bootstrap_cka_f32(const float* K, const float* L, int64_t n, int64_t ld, const int32_t* idx, int64_t k,
                          int64_t n_sets, int full_first, double* scores, void* ws, size_t ws_bytes, void* stream) {
-  clear_error();
-  VR_REQUIRE(n >= 0 && ld >= n && n_sets >= 0 && k >= 0 && k <= n,
-             "vr_bootstrap_cka_f32: bad shape n=%lld ld=%lld k=%lld n_sets=%lld", (long long)n, (long long)ld,
-             (long long)k, (long long)n_sets);
-  const int off = full_first ? 1 : 0;
-  const int64_t total = n_sets + off;
-  // every call fits the workspace of its (n, n_sets): the layout is monotone in both
-  const size_t need = cb_layout(nullptr, n, total).bytes;
-  if (ws_bytes < need || ws == nullptr) {
-    set_error("vr_bootstrap_cka_f32: workspace %zu < %zu", ws_bytes, need);
-    return VR_EWORKSPACE;
-  }
-  if (total == 0) return VR_OK;
-  VR_REQUIRE(scores != nullptr && (n_sets == 0 || idx != nullptr) && (n < 2 || (K != nullptr && L != nullptr)),
-             "vr_bootstrap_cka_f32: null pointer");
-  hipStream_t st = as_stream(stream);
-  if (n < 2) {  // a single stimulus centres to zero
-    k_ckaboot_nan<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(scores, total);
-    VR_CHECK_LAUNCH();
-    return VR_OK;
-  }
-  const CbLayout Y = cb_layout(ws, n, total);
-  VR_TRY(pboot_build_w(Y.W, idx, n, k, n_sets, Y.n_pad, Y.s_pad, off, st));
-  k_cka_shift_rows<<<(unsigned)n, 256, 0, st>>>(K, L, n, ld, Y.part);
-  VR_CHECK_LAUNCH();
-  VR_TRY(pboot_shift(Y.part, n, (double)n * (double)n, Y.shift, st));
-  CbParams P;
-  P.K = K;
-  P.L = L;
-  P.n = n;
-  P.ld = ld;
-  P.W = Y.W;
-  P.s_pad = Y.s_pad;
-  P.shift = Y.shift;
-  P.partial = Y.partial;
-  P.ST = Y.ST;
-  P.vec = (ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(K) & 15) == 0) && ((reinterpret_cast<uintptr_t>(L) & 15) == 0);
-  k_ckaboot<<<(unsigned)(Y.T * Y.ST), CB_THREADS, 0, st>>>(P);
-  VR_CHECK_LAUNCH();
-  k_ckaboot_reduce<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(Y.partial, Y.T, Y.s_pad, total, off, (double)n,
-                                                                   (double)k, Y.shift, scores, Y.flags);
-  VR_CHECK_LAUNCH();
-  // the one read-back of the call: which subsets the one-pass traces could not decide
-  std::vector<int32_t> flags((size_t)total);
-  VR_CHECK_HIP(hipMemcpyAsync(flags.data(), Y.flags, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  VR_CHECK_HIP(hipStreamSynchronize(st));
-  for (int64_t s = 0; s < total; ++s) {
-    if (!flags[(size_t)s]) continue;
-    if (off && s == 0)
-      VR_TRY(cka_two_pass(K, L, n, ld, nullptr, scores, 1, Y.part, Y.mu, st));
-    else
-      VR_TRY(cka_two_pass(K, L, k, ld, idx + (s - off) * k, scores + s, 1, Y.part, Y.mu, st));
-  }
-  return VR_OK;
+  return subset_bootstrap(CKA_BOOT, K, L, n, ld, idx, k, n_sets, full_first, scores, ws, ws_bytes, stream);
 }
 
 size_t vr_cka_subset_workspace(int64_t k) { return cka_subset_ws(k, nullptr, nullptr, nullptr); }

@@ -9,24 +9,20 @@
 //             float32 sum. One workgroup per 64 columns keeps that order exactly: 15
 //             waves stream rows into an LDS ring, wave 0 adds them in order. Bit-identical
 //             to numpy; `init` continues a sum (the multi-GPU chain over row shards).
-// k_cov       upper-triangle 64 x 64 tiles of the centred Gram in fp64 on the fp64 MFMA
-//             (v_mfma_f64_16x16x4_f64): 16-row stages of both column panels are centred
-//             in fp64 ((double)x - (double)mean, exact, as astype(float64) - mean) while
-//             they are staged into LDS, double-buffered; 4 waves as 2 x 2, each 32 x 32.
-//             The rows are split into S slices so small p still fills the chip; a slice
-//             writes its fp64 partial tile and k_cov_reduce adds the slices in fixed order,
-//             divides by the denominator and writes each entry and its mirror (the result
-//             is exactly symmetric, like the reference's batch.T @ batch).
+// k_cov       upper-triangle 64 x 64 tiles of the centred Gram in fp64 on tile64.h's pipeline
+//             (fp64 MFMA, 16-row stages, double-buffered LDS, row slices): both column panels
+//             are centred in fp64 ((double)x - (double)mean, exact, as astype(float64) - mean)
+//             while they are staged; a diagonal tile stages one panel for both operands.
+//             k_cov_reduce adds the slices in fixed order, divides by the denominator and
+//             writes each entry and its mirror (the result is exactly symmetric, like the
+//             reference's batch.T @ batch).
 //             k_cov<.., true> centres about an fp64 mean instead (the eigenspectrum's Gram,
 //             vr_centred_gram64_f32): per column as above, or, read transposed, per contraction
 //             index for the n x n form.
 // Roofline: fp64 MFMA, algorithmic FLOPs = n p (p + 1) (the unique entries i <= j).
-#include "internal.h"
+#include "tile64.h"
 
 namespace vr {
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-typedef float cf32x4 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------------------------
 // column sums in numpy's order
@@ -75,23 +71,17 @@ __global__ void k_col_div(const float* __restrict__ sum, int64_t p, float cnt, f
 }
 
 // ------------------------------------------------------------------------------------
-// fp64 covariance tiles
+// fp64 covariance tiles (tile64.h)
 // ------------------------------------------------------------------------------------
-constexpr int CT = 64;          // tile edge (columns of X)
-constexpr int CK = 16;          // rows per stage
-constexpr int CLD = CT + 16;    // LDS row pitch (doubles): 4 k-rows of a fragment read hit 2 bank sets
-constexpr int C_THREADS = 256;
-constexpr int C_STAGE = CK * CLD;  // doubles per panel per stage
-
 struct CovParams {
   const float* X;
   int64_t n, p, ldx;
   const float* mean;  // null: uncentred (the ridge Grams)
-  double* partial;  // [S][ntile][CT * CT]
+  double* partial;  // [S][ntile][T64 * T64]
   int T;            // tile rows
   int ntile;        // T (T + 1) / 2
   int S;            // row slices
-  int64_t kslice;   // rows per slice (multiple of CK)
+  int64_t kslice;   // rows per slice (multiple of T64_K)
   bool vec;         // 16-B aligned rows: float4 panel loads
   const double* mean64;  // k_cov<.., true>: the fp64 mean (length p, or n of the contraction when TRANS)
 };
@@ -99,14 +89,14 @@ struct CovParams {
 // TRANS (the kernel-form ridge Gram X X^T of a row-major (p, n) X): the contraction runs
 // along X's rows, so panel entry (k, c) is X[c * ldx + k]. Each thread loads 4 consecutive
 // k of one column c (one float4 when aligned) and scatters them down the LDS column.
-__device__ inline cf32x4 cov_load_t(const CovParams& P, int64_t col0, int64_t k, int64_t k1) {
+__device__ inline f32x4 cov_load_t(const CovParams& P, int64_t col0, int64_t k, int64_t k1) {
   const int c = threadIdx.x >> 2, kq = (threadIdx.x & 3) * 4;
-  cf32x4 v = {0.f, 0.f, 0.f, 0.f};
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
   const int64_t col = col0 + c, r = k + kq;
   if (col >= P.p || r >= k1) return v;
   const float* src = P.X + col * P.ldx + r;
   if (P.vec && r + 4 <= k1) {
-    v = *reinterpret_cast<const cf32x4*>(src);
+    v = *reinterpret_cast<const f32x4*>(src);
   } else {
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = (r + e < k1) ? src[e] : 0.f;
@@ -114,21 +104,21 @@ __device__ inline cf32x4 cov_load_t(const CovParams& P, int64_t col0, int64_t k,
   return v;
 }
 
-__device__ inline void cov_store_t(double* lds, const cf32x4 v) {
+__device__ inline void cov_store_t(double* lds, const f32x4 v) {
   const int c = threadIdx.x >> 2, kq = (threadIdx.x & 3) * 4;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) lds[(kq + e) * CLD + c] = (double)v[e];  // out-of-range entries are 0
+  for (int e = 0; e < 4; ++e) lds[(kq + e) * T64_LD + c] = (double)v[e];  // out-of-range entries are 0
 }
 
 // ... centred about the fp64 mean of the contraction index (the rows-side centred Gram)
-__device__ inline void cov_store_t64(const CovParams& P, double* lds, const cf32x4 v, int64_t col0, int64_t k,
+__device__ inline void cov_store_t64(const CovParams& P, double* lds, const f32x4 v, int64_t col0, int64_t k,
                                      int64_t k1) {
   const int c = threadIdx.x >> 2, kq = (threadIdx.x & 3) * 4;
   const bool cin = col0 + c < P.p;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const int64_t r = k + kq + e;
-    lds[(kq + e) * CLD + c] = (cin && r < k1) ? (double)v[e] - P.mean64[r] : 0.0;
+    lds[(kq + e) * T64_LD + c] = (cin && r < k1) ? (double)v[e] - P.mean64[r] : 0.0;
   }
 }
 
@@ -143,45 +133,19 @@ __device__ inline void cov_tile(int t, int T, int& bi, int& bj) {
   bj = r + (t - start);
 }
 
-// this thread's 4 columns of a 16-row panel stage: row kr = tid >> 4, columns 4 (tid & 15)
-__device__ inline cf32x4 cov_load(const CovParams& P, int64_t col0, int64_t k, int64_t k1) {
-  const int kr = threadIdx.x >> 4, c = (threadIdx.x & 15) * 4;
-  const int64_t r = k + kr;
-  cf32x4 v = {0.f, 0.f, 0.f, 0.f};
-  if (r >= k1) return v;
-  const float* src = P.X + r * P.ldx + col0 + c;
-  if (P.vec && col0 + c + 4 <= P.p) {
-    v = *reinterpret_cast<const cf32x4*>(src);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = (col0 + c + e < P.p) ? src[e] : 0.f;
-  }
-  return v;
-}
-
-__device__ inline void cov_store(double* lds, const cf32x4 v, const double m[4], int64_t k, int64_t k1) {
-  const int kr = threadIdx.x >> 4, c = (threadIdx.x & 15) * 4;
-  const bool in = k + kr < k1;
-  double* dst = lds + kr * CLD + c;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) dst[e] = in ? (double)v[e] - m[e] : 0.0;  // padded rows add exact zeros
-}
-
 // M64: centre about P.mean64 (fp64) instead of P.mean (fp32)
 template <bool TRANS, bool M64 = false>
-__global__ __launch_bounds__(C_THREADS, 2) void k_cov(CovParams P) {
-  __shared__ __attribute__((aligned(16))) double lds[2][2][C_STAGE];  // [buf][A/B]
+__global__ __launch_bounds__(T64_THREADS, 2) void k_cov(CovParams P) {
+  __shared__ __attribute__((aligned(16))) double lds[2][2][T64_STAGE];  // [buf][A/B]
   const int id = (int)xcd_remap(blockIdx.x, gridDim.x);
   const int tile = id / P.S, slice = id % P.S;
   int bi, bj;
   cov_tile(tile, P.T, bi, bj);
   const bool diag = bi == bj;
-  const int64_t ci = (int64_t)bi * CT, cj = (int64_t)bj * CT;
+  const int64_t ci = (int64_t)bi * T64, cj = (int64_t)bj * T64;
   const int64_t k0 = (int64_t)slice * P.kslice;
   const int64_t k1 = min(P.n, k0 + P.kslice);
-  const int nk = k1 > k0 ? (int)((k1 - k0 + CK - 1) / CK) : 0;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int wr = wid >> 1, wc = wid & 1;
+  const int nk = k1 > k0 ? (int)((k1 - k0 + T64_K - 1) / T64_K) : 0;
 
   double mA[4], mB[4];
   {
@@ -197,75 +161,20 @@ __global__ __launch_bounds__(C_THREADS, 2) void k_cov(CovParams P) {
       }
     }
   }
-  f64x4 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = f64x4{0.0, 0.0, 0.0, 0.0};
-
-  auto load = [&](int64_t col0, int64_t k) { return TRANS ? cov_load_t(P, col0, k, k1) : cov_load(P, col0, k, k1); };
-  auto store = [&](double* dst, const cf32x4 v, const double* m, int64_t k) {
+  // TRANS loads hold float4s of 4 consecutive k of one column (see tile64.h on why these stay here)
+  auto load = [&](int side, int64_t k) {
+    const int64_t col0 = side ? cj : ci;
+    return TRANS ? cov_load_t(P, col0, k, k1) : panel_load(P.X, P.ldx, P.p, P.vec, nullptr, col0, k, k1);
+  };
+  auto store = [&](int side, double* dst, const f32x4 v, int64_t k) {
     if constexpr (TRANS && M64)
-      cov_store_t64(P, dst, v, m == mA ? ci : cj, k, k1);  // m names the panel: mA goes with ci
+      cov_store_t64(P, dst, v, side ? cj : ci, k, k1);
     else if constexpr (TRANS)
       cov_store_t(dst, v);
     else
-      cov_store(dst, v, m, k, k1);
+      panel_store(dst, v, side ? mB : mA, k, k1);
   };
-  cf32x4 ga = {0.f, 0.f, 0.f, 0.f}, gb = ga;
-  if (nk > 0) {
-    ga = load(ci, k0);
-    if (!diag) gb = load(cj, k0);
-    store(lds[0][0], ga, mA, k0);
-    if (!diag) store(lds[0][1], gb, mB, k0);
-  }
-  __syncthreads();
-  // fragment of the 16x16x4 f64 MFMA: lane l supplies A[m = l & 15][k = l >> 4] and
-  // B[k = l >> 4][n = l & 15]; here A = X^T (panel of columns ci), B = X (columns cj)
-  const int fk = lane >> 4, fm = lane & 15;
-  for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    const double* As = lds[cur][0];
-    const double* Bs = diag ? As : lds[cur][1];
-    const bool more = kt + 1 < nk;
-    const int64_t kn = k0 + (int64_t)(kt + 1) * CK;
-    if (more) {
-      ga = load(ci, kn);
-      if (!diag) gb = load(cj, kn);
-    }
-#pragma unroll
-    for (int ks = 0; ks < CK / 4; ++ks) {
-      const int kr = ks * 4 + fk;
-      double a[2], b[2];
-#pragma unroll
-      for (int m = 0; m < 2; ++m) {
-        a[m] = As[kr * CLD + wr * 32 + m * 16 + fm];
-        b[m] = Bs[kr * CLD + wc * 32 + m * 16 + fm];
-      }
-#pragma unroll
-      for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int nn = 0; nn < 2; ++nn)
-          acc[m][nn] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[m], b[nn], acc[m][nn], 0, 0, 0);
-    }
-    if (more) {
-      store(lds[cur ^ 1][0], ga, mA, kn);
-      if (!diag) store(lds[cur ^ 1][1], gb, mB, kn);
-    }
-    __syncthreads();
-  }
-  // C/D of the f64 MFMA: col = lane & 15, row = (lane >> 4) + 4 r
-  double* out = P.partial + ((int64_t)slice * P.ntile + tile) * (CT * CT);
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int nn = 0; nn < 2; ++nn)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int li = wr * 32 + m * 16 + fk + 4 * r;
-        const int lj = wc * 32 + nn * 16 + fm;
-        out[li * CT + lj] = acc[m][nn][r];
-      }
+  tile_pipeline(lds, k0, nk, diag, load, store, P.partial + ((int64_t)slice * P.ntile + tile) * (T64 * T64));
 }
 
 // sum of the slices in slice order, / denom, into cov (entry and mirror)
@@ -275,28 +184,26 @@ __global__ __launch_bounds__(256) void k_cov_reduce(const double* __restrict__ p
   const int tile = blockIdx.x;
   int bi, bj;
   cov_tile(tile, T, bi, bj);
-  const int64_t ci = (int64_t)bi * CT, cj = (int64_t)bj * CT;
-  for (int e = threadIdx.x; e < CT * CT; e += blockDim.x) {
-    const int li = e / CT, lj = e % CT;
+  const int64_t ci = (int64_t)bi * T64, cj = (int64_t)bj * T64;
+  for (int e = threadIdx.x; e < T64 * T64; e += blockDim.x) {
+    const int li = e / T64, lj = e % T64;
     const int64_t i = ci + li, j = cj + lj;
     if (i >= p || j >= p || (bi == bj && li > lj)) continue;
-    double s = 0.0;
-    for (int q = 0; q < S; ++q) s += partial[((int64_t)q * ntile + tile) * (CT * CT) + e];
-    s /= denom;
+    const double s = slice_sum(partial, S, ntile, tile, e) / denom;
     cov[i * ldc + j] = s;
     if (i != j) cov[j * ldc + i] = s;
   }
 }
 
 static void cov_geometry(int64_t n, int64_t p, int& T, int& ntile, int& S, int64_t& kslice) {
-  T = (int)((p + CT - 1) / CT);
+  T = (int)((p + T64 - 1) / T64);
   ntile = T * (T + 1) / 2;
   // enough workgroups for ~4 per CU, each slice at least 64 stages of rows
   const int64_t want = std::max<int64_t>(1, (4LL * num_cus() + ntile - 1) / ntile);
-  const int64_t maxs = std::max<int64_t>(1, n / (64 * CK));
+  const int64_t maxs = std::max<int64_t>(1, n / (64 * T64_K));
   S = (int)std::min<int64_t>(want, maxs);
-  kslice = ((n + S - 1) / S + CK - 1) / CK * CK;
-  if (kslice == 0) kslice = CK;
+  kslice = ((n + S - 1) / S + T64_K - 1) / T64_K * T64_K;
+  if (kslice == 0) kslice = T64_K;
   S = (int)std::max<int64_t>(1, (n + kslice - 1) / kslice);
 }
 
@@ -349,7 +256,7 @@ size_t vr_pca_cov_workspace(int64_t n, int64_t p) {
   int64_t kslice;
   cov_launch_geometry(n, p, T, ntile, S, kslice);
   Carver c(nullptr);
-  c.take<double>((size_t)S * ntile * CT * CT);
+  c.take<double>((size_t)S * ntile * T64 * T64);
   return c.bytes();
 }
 
@@ -366,18 +273,18 @@ static int cov_launch(bool trans, const float* X, int64_t n, int64_t p, int64_t 
   P.mean = mean;
   cov_launch_geometry(n, p, P.T, P.ntile, P.S, P.kslice);
   Carver c(ws);
-  P.partial = c.take<double>((size_t)P.S * P.ntile * CT * CT);
+  P.partial = c.take<double>((size_t)P.S * P.ntile * T64 * T64);
   P.vec = (ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(X) & 15) == 0);
   {
     KtScope kt(KT_COV, (double)n * (double)p * (double)(p + 1), st);  // algorithmic FLOPs
     if (mean64 != nullptr && trans)
-      k_cov<true, true><<<(unsigned)(P.ntile * P.S), C_THREADS, 0, st>>>(P);
+      k_cov<true, true><<<(unsigned)(P.ntile * P.S), T64_THREADS, 0, st>>>(P);
     else if (mean64 != nullptr)
-      k_cov<false, true><<<(unsigned)(P.ntile * P.S), C_THREADS, 0, st>>>(P);
+      k_cov<false, true><<<(unsigned)(P.ntile * P.S), T64_THREADS, 0, st>>>(P);
     else if (trans)
-      k_cov<true><<<(unsigned)(P.ntile * P.S), C_THREADS, 0, st>>>(P);
+      k_cov<true><<<(unsigned)(P.ntile * P.S), T64_THREADS, 0, st>>>(P);
     else
-      k_cov<false><<<(unsigned)(P.ntile * P.S), C_THREADS, 0, st>>>(P);
+      k_cov<false><<<(unsigned)(P.ntile * P.S), T64_THREADS, 0, st>>>(P);
     VR_CHECK_LAUNCH();
   }
   k_cov_reduce<<<(unsigned)P.ntile, 256, 0, st>>>(P.partial, P.S, P.ntile, P.T, p, denom, cov, ldc);

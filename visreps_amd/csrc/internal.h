@@ -39,15 +39,6 @@ int radix_sort_kv(uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, uint32_t* 
 int pearson_two_pass(const float* A, const float* B, int64_t n_or_k, int64_t ld, const int32_t* idx,
                      double* out, double* part, double* mu, hipStream_t st);
 
-// ---- subset-indicator panels and shifts of the masked-GEMM engines (pearson_boot.hip) --
-// W: n_pad x s_pad bytes (both multiples of 64), W[i][off + s] = 1 iff stimulus i is in row s of
-// idx (n_sets x k), column 0 all ones over the rows < n when off == 1, 0 elsewhere. An index
-// outside [0, n) is skipped, never written.
-int pboot_build_w(uint8_t* W, const int32_t* idx, int64_t n, int64_t k, int64_t n_sets, int64_t n_pad,
-                  int64_t s_pad, int off, hipStream_t st);
-// shift[q] = float32((sum_a part[2 a + q]) / M) as a double, 0 if that is not finite (q = 0, 1)
-int pboot_shift(const double* part, int64_t n, double M, double* shift, hipStream_t st);
-
 // ---- two-pass fp64 CKA traces of two kernel matrices (cka_boot.hip) -----------------
 // idx == nullptr: the full n_or_k x n_or_k matrices; else K[idx][:, idx], L[idx][:, idx] read in
 // place. part: 5 n_or_k doubles, mu: 2 doubles. out: n_out doubles, 1 (the CKA) or 4 (CKA,
@@ -87,6 +78,40 @@ __device__ inline uint32_t block_exclusive_scan(uint32_t v, uint32_t* lds, uint3
   total = lds[BS / 64];
   __syncthreads();
   return r;
+}
+
+// Vector registers of the fp64-MFMA engines (tile64.h, subset_gemm.h).
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// Block sum of Q doubles per thread, 256 threads, red[Q][4] in LDS: a shuffle tree per wave,
+// then the four wave sums in wave order. The sums feed fp64 results, so each caller keeps the
+// association it has always had: PAIRS adds (r0 + r1) + (r2 + r3), else r0 + r1 + r2 + r3.
+// block_sum_waves leaves the wave sums in red (barrier included) for callers where one thread
+// per quantity finishes; block_sum hands every thread every total.
+template <int Q>
+__device__ inline void block_sum_waves(const double (&v)[Q], double (*red)[4]) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    double t = v[q];
+    for (int o = 32; o > 0; o >>= 1) t += __shfl_down(t, o, 64);
+    if (lane == 0) red[q][w] = t;
+  }
+  __syncthreads();
+}
+
+template <bool PAIRS>
+__device__ inline double block_sum_total(const double (&r)[4]) {
+  return PAIRS ? (r[0] + r[1]) + (r[2] + r[3]) : r[0] + r[1] + r[2] + r[3];
+}
+
+template <int Q, bool PAIRS>
+__device__ inline void block_sum(const double (&v)[Q], double (*red)[4], double (&out)[Q]) {
+  block_sum_waves<Q>(v, red);
+#pragma unroll
+  for (int q = 0; q < Q; ++q) out[q] = block_sum_total<PAIRS>(red[q]);
 }
 
 // Padded LDS index for tiles read both striped (lane-contiguous) and blocked (16

@@ -41,19 +41,9 @@ __global__ __launch_bounds__(256) void k_pearson_rows(const float* __restrict__ 
       s4 += dy * dy;
     }
   }
-  double v[5] = {s0, s1, s2, s3, s4};
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int q = 0; q < 5; ++q) {
-    double t = v[q];
-    for (int o = 32; o > 0; o >>= 1) t += __shfl_down(t, o, 64);
-    if (lane == 0) red[q][w] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < 5) {
-    const int q = threadIdx.x;
-    part[a * 5 + q] = red[q][0] + red[q][1] + red[q][2] + red[q][3];
-  }
+  const double v[5] = {s0, s1, s2, s3, s4};
+  block_sum_waves<5>(v, red);
+  if (threadIdx.x < 5) part[a * 5 + threadIdx.x] = block_sum_total<false>(red[threadIdx.x]);
 }
 
 __global__ __launch_bounds__(256) void k_pearson_reduce(const double* __restrict__ part,
@@ -64,17 +54,10 @@ __global__ __launch_bounds__(256) void k_pearson_reduce(const double* __restrict
   double v[5] = {0, 0, 0, 0, 0};
   for (int64_t a = threadIdx.x; a < n; a += 256)
     for (int q = 0; q < 5; ++q) v[q] += part[a * 5 + q];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int q = 0; q < 5; ++q) {
-    double t = v[q];
-    for (int o = 32; o > 0; o >>= 1) t += __shfl_down(t, o, 64);
-    if (lane == 0) red[q][w] = t;
-  }
-  __syncthreads();
+  block_sum_waves<5>(v, red);
   if (threadIdx.x == 0) {
     double s[5];
-    for (int q = 0; q < 5; ++q) s[q] = red[q][0] + red[q][1] + red[q][2] + red[q][3];
+    for (int q = 0; q < 5; ++q) s[q] = block_sum_total<false>(red[q]);
     if (stage == 0) {
       mu[0] = s[0] / M;
       mu[1] = s[1] / M;

@@ -14,15 +14,15 @@
 // sigma_j with eigenvector [u_j; v_j] / sqrt(2), which vr_eigh_top_f64 (eigvals.hip) solves with
 // no squaring of the condition number.
 //
-// k_xcov           64 x 64 tiles of the p x q rectangle on the fp64 MFMA (v_mfma_f64_16x16x4_f64),
-//                  k_cov's tiling: 16-row stages of the X and Y panels centred in fp64 while staged
-//                  into LDS, double-buffered, 4 waves as 2 x 2 of 32 x 32. One launch per segment;
-//                  a segment is cut into S row slices, k_xcov_reduce adds the slices in order.
+// k_xcov           64 x 64 tiles of the p x q rectangle on tile64.h's pipeline (fp64 MFMA, 16-row
+//                  stages, double-buffered LDS): the X and Y panels are centred in fp64 while
+//                  staged. One launch per segment; a segment is cut into S row slices,
+//                  k_xcov_reduce adds the slices in order.
 // k_seg_colstats   per-segment column sums and sums of squares of the same centred values.
 // k_fold_stats     training mean and standard deviation of one fold from the segment statistics.
 // k_fold_assemble  J of one fold (exactly symmetric, exactly zero diagonal blocks).
 // k_xgemm_nt       G[i, j] = sum_k (A[i, k] - a_mean[k]) B[j, k], both operands K-contiguous, on
-//                  the same tiles with split-K: the projection Z = X R^T (products of two fp32
+//                  the same pipeline with split-K: the projection Z = X R^T (products of two fp32
 //                  values are exact in fp64, the sum is rounded once to fp32) and the test scores.
 // k_svd_extract    u, v from the eigenvector rows: halves normalised, svd_flip's u-based sign,
 //                  divided by the training standard deviation; null components flagged.
@@ -35,19 +35,9 @@
 #include <cfloat>
 #include <cmath>
 
-#include "internal.h"
+#include "tile64.h"
 
 namespace vr {
-
-typedef double xf64x4 __attribute__((ext_vector_type(4)));
-typedef double xf64x2 __attribute__((ext_vector_type(2)));
-typedef float xf32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int XT = 64;          // tile edge
-constexpr int XK = 16;          // contraction entries per stage
-constexpr int XLD = XT + 16;    // LDS row pitch (doubles), as k_cov
-constexpr int X_THREADS = 256;
-constexpr int X_STAGE = XK * XLD;
 
 // ------------------------------------------------------------------------------------
 // segmented cross-moments
@@ -59,83 +49,21 @@ struct XcovParams {
   const int32_t* rows;  // nullable: position r of the fold order -> row of X and Y
   const double* mx;     // global column means
   const double* my;
-  double* partial;      // this segment's [S][ntile][XT * XT]
+  double* partial;      // this segment's [S][ntile][T64 * T64]
   int TJ, ntile, S;
-  int64_t k0, k1, kslice;  // the segment's positions [k0, k1), positions per slice (multiple of XK)
+  int64_t k0, k1, kslice;  // the segment's positions [k0, k1), positions per slice (multiple of T64_K)
   bool vecx, vecy;
 };
 
-// this thread's 4 columns of a 16-row stage: row kr = tid >> 4, columns 4 (tid & 15)
-__device__ inline xf32x4 xcov_load(const float* M, int64_t ld, int64_t ncol, bool vec, const int32_t* rows,
-                                   int64_t col0, int64_t k, int64_t k1) {
-  const int kr = threadIdx.x >> 4, c = (threadIdx.x & 15) * 4;
-  const int64_t r = k + kr;
-  xf32x4 v = {0.f, 0.f, 0.f, 0.f};
-  if (r >= k1) return v;
-  const int64_t row = rows != nullptr ? (int64_t)rows[r] : r;
-  const float* src = M + row * ld + col0 + c;
-  if (vec && col0 + c + 4 <= ncol) {
-    v = *reinterpret_cast<const xf32x4*>(src);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = (col0 + c + e < ncol) ? src[e] : 0.f;
-  }
-  return v;
-}
-
-__device__ inline void xcov_store(double* lds, const xf32x4 v, const double m[4], int64_t k, int64_t k1) {
-  const int kr = threadIdx.x >> 4, c = (threadIdx.x & 15) * 4;
-  const bool in = k + kr < k1;
-  double* dst = lds + kr * XLD + c;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) dst[e] = in ? (double)v[e] - m[e] : 0.0;  // padded rows add exact zeros
-}
-
-// 16 stages of MFMAs on one LDS stage pair: A panel entry (k, i), B panel entry (k, j)
-__device__ inline void x_mma_stage(const double* As, const double* Bs, int wr, int wc, int fk, int fm,
-                                   xf64x4 acc[2][2]) {
-#pragma unroll
-  for (int ks = 0; ks < XK / 4; ++ks) {
-    const int kr = ks * 4 + fk;
-    double a[2], b[2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-      a[m] = As[kr * XLD + wr * 32 + m * 16 + fm];
-      b[m] = Bs[kr * XLD + wc * 32 + m * 16 + fm];
-    }
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int nn = 0; nn < 2; ++nn)
-        acc[m][nn] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[m], b[nn], acc[m][nn], 0, 0, 0);
-  }
-}
-
-// C/D of the f64 MFMA: col = lane & 15, row = (lane >> 4) + 4 r
-__device__ inline void x_store_tile(double* out, int wr, int wc, int fk, int fm, const xf64x4 acc[2][2]) {
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int nn = 0; nn < 2; ++nn)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int li = wr * 32 + m * 16 + fk + 4 * r;
-        const int lj = wc * 32 + nn * 16 + fm;
-        out[li * XT + lj] = acc[m][nn][r];
-      }
-}
-
-__global__ __launch_bounds__(X_THREADS, 2) void k_xcov(XcovParams P) {
-  __shared__ __attribute__((aligned(16))) double lds[2][2][X_STAGE];  // [buf][X/Y]
+__global__ __launch_bounds__(T64_THREADS, 2) void k_xcov(XcovParams P) {
+  __shared__ __attribute__((aligned(16))) double lds[2][2][T64_STAGE];  // [buf][X/Y]
   const int id = (int)xcd_remap(blockIdx.x, gridDim.x);
   const int tile = id / P.S, slice = id % P.S;
   const int bi = tile / P.TJ, bj = tile % P.TJ;
-  const int64_t ci = (int64_t)bi * XT, cj = (int64_t)bj * XT;
+  const int64_t ci = (int64_t)bi * T64, cj = (int64_t)bj * T64;
   const int64_t k0 = min(P.k1, P.k0 + (int64_t)slice * P.kslice);
   const int64_t k1 = min(P.k1, k0 + P.kslice);
-  const int nk = (int)((k1 - k0 + XK - 1) / XK);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int wr = wid >> 1, wc = wid & 1;
+  const int nk = (int)((k1 - k0 + T64_K - 1) / T64_K);
 
   double mA[4], mB[4];
   {
@@ -146,38 +74,13 @@ __global__ __launch_bounds__(X_THREADS, 2) void k_xcov(XcovParams P) {
       mB[e] = (cj + c + e < P.q) ? P.my[cj + c + e] : 0.0;
     }
   }
-  xf64x4 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = xf64x4{0.0, 0.0, 0.0, 0.0};
-
-  xf32x4 ga = {0.f, 0.f, 0.f, 0.f}, gb = ga;
-  if (nk > 0) {
-    ga = xcov_load(P.X, P.ldx, P.p, P.vecx, P.rows, ci, k0, k1);
-    gb = xcov_load(P.Y, P.ldy, P.q, P.vecy, P.rows, cj, k0, k1);
-    xcov_store(lds[0][0], ga, mA, k0, k1);
-    xcov_store(lds[0][1], gb, mB, k0, k1);
-  }
-  __syncthreads();
-  const int fk = lane >> 4, fm = lane & 15;
-  for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    const bool more = kt + 1 < nk;
-    const int64_t kn = k0 + (int64_t)(kt + 1) * XK;
-    if (more) {
-      ga = xcov_load(P.X, P.ldx, P.p, P.vecx, P.rows, ci, kn, k1);
-      gb = xcov_load(P.Y, P.ldy, P.q, P.vecy, P.rows, cj, kn, k1);
-    }
-    x_mma_stage(lds[cur][0], lds[cur][1], wr, wc, fk, fm, acc);
-    if (more) {
-      xcov_store(lds[cur ^ 1][0], ga, mA, kn, k1);
-      xcov_store(lds[cur ^ 1][1], gb, mB, kn, k1);
-    }
-    __syncthreads();
-  }
+  auto load = [&](int side, int64_t k) {
+    return side ? panel_load(P.Y, P.ldy, P.q, P.vecy, P.rows, cj, k, k1)
+                : panel_load(P.X, P.ldx, P.p, P.vecx, P.rows, ci, k, k1);
+  };
+  auto store = [&](int side, double* dst, const f32x4 v, int64_t k) { panel_store(dst, v, side ? mB : mA, k, k1); };
   // an empty slice (or an empty segment) stores its all-zero tile
-  x_store_tile(P.partial + ((int64_t)slice * P.ntile + tile) * (XT * XT), wr, wc, fk, fm, acc);
+  tile_pipeline(lds, k0, nk, false, load, store, P.partial + ((int64_t)slice * P.ntile + tile) * (T64 * T64));
 }
 
 // S_f = sum of the slices in slice order; grid (ntile, F)
@@ -186,14 +89,12 @@ __global__ __launch_bounds__(256) void k_xcov_reduce(const double* __restrict__ 
   const int tile = blockIdx.x;
   const int64_t f = blockIdx.y;
   const int bi = tile / TJ, bj = tile % TJ;
-  const double* part = partial + f * (int64_t)S * ntile * (XT * XT);
+  const double* part = partial + f * (int64_t)S * ntile * (T64 * T64);
   double* o = out + f * p * q;
-  for (int e = threadIdx.x; e < XT * XT; e += blockDim.x) {
-    const int64_t i = (int64_t)bi * XT + e / XT, j = (int64_t)bj * XT + e % XT;
+  for (int e = threadIdx.x; e < T64 * T64; e += blockDim.x) {
+    const int64_t i = (int64_t)bi * T64 + e / T64, j = (int64_t)bj * T64 + e % T64;
     if (i >= p || j >= q) continue;
-    double s = 0.0;
-    for (int z = 0; z < S; ++z) s += part[((int64_t)z * ntile + tile) * (XT * XT) + e];
-    o[i * q + j] = s;
+    o[i * q + j] = slice_sum(part, S, ntile, tile, e);
   }
 }
 
@@ -301,23 +202,23 @@ struct XgemmParams {
   int64_t M, N, K, lda, ldb;
   const int32_t* a_rows;  // nullable: row i of the product reads row a_rows[i] of A
   const double* a_mean;   // nullable, length K
-  double* partial;        // [S][ntile][XT * XT]
+  double* partial;        // [S][ntile][T64 * T64]
   int TJ, ntile, S;
-  int64_t kslice;         // contraction entries per slice (multiple of XK)
+  int64_t kslice;         // contraction entries per slice (multiple of T64_K)
   bool veca, vecb;
 };
 
 // this thread's 4 consecutive k of one row: row c = tid >> 2, k offset 4 (tid & 3)
-__device__ inline xf64x4 xg_load(const float* A, int64_t lda, int64_t nrow, bool vec, const int32_t* a_rows,
-                                 int64_t row0, int64_t k, int64_t k1) {
+__device__ inline f64x4 xg_load(const float* A, int64_t lda, int64_t nrow, bool vec, const int32_t* a_rows,
+                                int64_t row0, int64_t k, int64_t k1) {
   const int c = threadIdx.x >> 2, kq = (threadIdx.x & 3) * 4;
-  xf64x4 v = {0.0, 0.0, 0.0, 0.0};
+  f64x4 v = {0.0, 0.0, 0.0, 0.0};
   const int64_t i = row0 + c, r = k + kq;
   if (i >= nrow || r >= k1) return v;
   const int64_t row = a_rows != nullptr ? (int64_t)a_rows[i] : i;
   const float* src = A + row * lda + r;
   if (vec && r + 4 <= k1) {
-    const xf32x4 t = *reinterpret_cast<const xf32x4*>(src);
+    const f32x4 t = *reinterpret_cast<const f32x4*>(src);
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = (double)t[e];
   } else {
@@ -327,17 +228,17 @@ __device__ inline xf64x4 xg_load(const float* A, int64_t lda, int64_t nrow, bool
   return v;
 }
 
-__device__ inline xf64x4 xg_load(const double* B, int64_t ldb, int64_t nrow, bool vec, const int32_t*,
-                                 int64_t row0, int64_t k, int64_t k1) {
+__device__ inline f64x4 xg_load(const double* B, int64_t ldb, int64_t nrow, bool vec, const int32_t*,
+                                int64_t row0, int64_t k, int64_t k1) {
   const int c = threadIdx.x >> 2, kq = (threadIdx.x & 3) * 4;
-  xf64x4 v = {0.0, 0.0, 0.0, 0.0};
+  f64x4 v = {0.0, 0.0, 0.0, 0.0};
   const int64_t i = row0 + c, r = k + kq;
   if (i >= nrow || r >= k1) return v;
   const double* src = B + i * ldb + r;
   if (vec && r + 4 <= k1) {
-    const xf64x2 t0 = *reinterpret_cast<const xf64x2*>(src);
-    const xf64x2 t1 = *reinterpret_cast<const xf64x2*>(src + 2);
-    v = xf64x4{t0[0], t0[1], t1[0], t1[1]};
+    const f64x2 t0 = *reinterpret_cast<const f64x2*>(src);
+    const f64x2 t1 = *reinterpret_cast<const f64x2*>(src + 2);
+    v = f64x4{t0[0], t0[1], t1[0], t1[1]};
   } else {
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = (r + e < k1) ? src[e] : 0.0;
@@ -346,7 +247,7 @@ __device__ inline xf64x4 xg_load(const double* B, int64_t ldb, int64_t nrow, boo
 }
 
 // scatter the 4 k down the LDS column of row c; out-of-range entries stay exact zeros
-__device__ inline void xg_store(double* lds, const xf64x4 v, const double* mean, bool row_in, int64_t k,
+__device__ inline void xg_store(double* lds, const f64x4 v, const double* mean, bool row_in, int64_t k,
                                 int64_t k1) {
   const int c = threadIdx.x >> 2, kq = (threadIdx.x & 3) * 4;
 #pragma unroll
@@ -354,55 +255,31 @@ __device__ inline void xg_store(double* lds, const xf64x4 v, const double* mean,
     const int64_t r = k + kq + e;
     double x = v[e];
     if (mean != nullptr) x = (row_in && r < k1) ? x - mean[r] : 0.0;
-    lds[(kq + e) * XLD + c] = x;
+    lds[(kq + e) * T64_LD + c] = x;
   }
 }
 
 template <typename TB>
-__global__ __launch_bounds__(X_THREADS, 2) void k_xgemm_nt(XgemmParams<TB> P) {
-  __shared__ __attribute__((aligned(16))) double lds[2][2][X_STAGE];  // [buf][A/B]
+__global__ __launch_bounds__(T64_THREADS, 2) void k_xgemm_nt(XgemmParams<TB> P) {
+  __shared__ __attribute__((aligned(16))) double lds[2][2][T64_STAGE];  // [buf][A/B]
   const int id = (int)xcd_remap(blockIdx.x, gridDim.x);
   const int tile = id / P.S, slice = id % P.S;
   const int bi = tile / P.TJ, bj = tile % P.TJ;
-  const int64_t ri = (int64_t)bi * XT, rj = (int64_t)bj * XT;
+  const int64_t ri = (int64_t)bi * T64, rj = (int64_t)bj * T64;
   const int64_t k0 = min(P.K, (int64_t)slice * P.kslice);
   const int64_t k1 = min(P.K, k0 + P.kslice);
-  const int nk = (int)((k1 - k0 + XK - 1) / XK);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int wr = wid >> 1, wc = wid & 1;
+  const int nk = (int)((k1 - k0 + T64_K - 1) / T64_K);
   const bool a_in = ri + (threadIdx.x >> 2) < P.M;
 
-  xf64x4 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = xf64x4{0.0, 0.0, 0.0, 0.0};
-
-  xf64x4 ga = {0.0, 0.0, 0.0, 0.0}, gb = ga;
-  if (nk > 0) {
-    ga = xg_load(P.A, P.lda, P.M, P.veca, P.a_rows, ri, k0, k1);
-    gb = xg_load(P.B, P.ldb, P.N, P.vecb, nullptr, rj, k0, k1);
-    xg_store(lds[0][0], ga, P.a_mean, a_in, k0, k1);
-    xg_store(lds[0][1], gb, nullptr, true, k0, k1);
-  }
-  __syncthreads();
-  const int fk = lane >> 4, fm = lane & 15;
-  for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    const bool more = kt + 1 < nk;
-    const int64_t kn = k0 + (int64_t)(kt + 1) * XK;
-    if (more) {
-      ga = xg_load(P.A, P.lda, P.M, P.veca, P.a_rows, ri, kn, k1);
-      gb = xg_load(P.B, P.ldb, P.N, P.vecb, nullptr, rj, kn, k1);
-    }
-    x_mma_stage(lds[cur][0], lds[cur][1], wr, wc, fk, fm, acc);
-    if (more) {
-      xg_store(lds[cur ^ 1][0], ga, P.a_mean, a_in, kn, k1);
-      xg_store(lds[cur ^ 1][1], gb, nullptr, true, kn, k1);
-    }
-    __syncthreads();
-  }
-  x_store_tile(P.partial + ((int64_t)slice * P.ntile + tile) * (XT * XT), wr, wc, fk, fm, acc);
+  // both operands hold double4s of 4 consecutive k of one row (see tile64.h on why these stay here)
+  auto load = [&](int side, int64_t k) {
+    return side ? xg_load(P.B, P.ldb, P.N, P.vecb, nullptr, rj, k, k1)
+                : xg_load(P.A, P.lda, P.M, P.veca, P.a_rows, ri, k, k1);
+  };
+  auto store = [&](int side, double* dst, const f64x4 v, int64_t k) {
+    xg_store(dst, v, side ? nullptr : P.a_mean, side || a_in, k, k1);
+  };
+    tile_pipeline(lds, k0, nk, false, load, store, P.partial + ((int64_t)slice * P.ntile + tile) * (T64 * T64));
 }
 
 // G = sum of the split-K slices in slice order, rounded once to the output type
@@ -411,12 +288,10 @@ __global__ __launch_bounds__(256) void k_xgemm_reduce(const double* __restrict__
                                                       int64_t M, int64_t N, TO* __restrict__ G, int64_t ldg) {
   const int tile = blockIdx.x;
   const int bi = tile / TJ, bj = tile % TJ;
-  for (int e = threadIdx.x; e < XT * XT; e += blockDim.x) {
-    const int64_t i = (int64_t)bi * XT + e / XT, j = (int64_t)bj * XT + e % XT;
+  for (int e = threadIdx.x; e < T64 * T64; e += blockDim.x) {
+    const int64_t i = (int64_t)bi * T64 + e / T64, j = (int64_t)bj * T64 + e % T64;
     if (i >= M || j >= N) continue;
-    double s = 0.0;
-    for (int z = 0; z < S; ++z) s += partial[((int64_t)z * ntile + tile) * (XT * XT) + e];
-    G[i * ldg + j] = (TO)s;
+    G[i * ldg + j] = (TO)slice_sum(partial, S, ntile, tile, e);
   }
 }
 
@@ -530,17 +405,17 @@ struct XGeom {
 };
 
 // tiles of an M x N rectangle; the contraction of length K cut into S slices of kslice (a
-// multiple of XK) so that ~4 workgroups per CU exist where K allows, each slice >= min_stages stages
+// multiple of T64_K) so that ~4 workgroups per CU exist where K allows, each slice >= min_stages stages
 static XGeom x_geometry(int64_t M, int64_t N, int64_t K, int64_t groups, int min_stages) {
   XGeom g;
-  g.TI = (int)((M + XT - 1) / XT);
-  g.TJ = (int)((N + XT - 1) / XT);
+  g.TI = (int)((M + T64 - 1) / T64);
+  g.TJ = (int)((N + T64 - 1) / T64);
   g.ntile = g.TI * g.TJ;
   const int64_t wgs = std::max<int64_t>(1, (int64_t)g.ntile * std::max<int64_t>(groups, 1));
   const int64_t want = std::max<int64_t>(1, (4LL * num_cus() + wgs - 1) / wgs);
-  const int64_t maxs = std::max<int64_t>(1, K / ((int64_t)min_stages * XK));
+  const int64_t maxs = std::max<int64_t>(1, K / ((int64_t)min_stages * T64_K));
   const int64_t S = std::min<int64_t>({want, maxs, 64});
-  g.kslice = ((std::max<int64_t>(K, 1) + S - 1) / S + XK - 1) / XK * XK;
+  g.kslice = ((std::max<int64_t>(K, 1) + S - 1) / S + T64_K - 1) / T64_K * T64_K;
   g.S = (int)std::max<int64_t>(1, (std::max<int64_t>(K, 1) + g.kslice - 1) / g.kslice);
   return g;
 }
@@ -564,14 +439,14 @@ static int xgemm_launch(const float* A, int64_t M, int64_t K, int64_t lda, const
   P.a_rows = a_rows;
   P.a_mean = a_mean;
   Carver c(ws);
-  P.partial = c.take<double>((size_t)g.S * g.ntile * XT * XT);
+  P.partial = c.take<double>((size_t)g.S * g.ntile * T64 * T64);
   P.TJ = g.TJ;
   P.ntile = g.ntile;
   P.S = g.S;
   P.kslice = g.kslice;
   P.veca = (lda % 4 == 0) && aligned16(A);
   P.vecb = (ldb % (16 / (int64_t)sizeof(TB)) == 0) && aligned16(B);
-  k_xgemm_nt<TB><<<(unsigned)(g.ntile * g.S), X_THREADS, 0, st>>>(P);
+  k_xgemm_nt<TB><<<(unsigned)(g.ntile * g.S), T64_THREADS, 0, st>>>(P);
   VR_CHECK_LAUNCH();
   k_xgemm_reduce<TO><<<(unsigned)g.ntile, 256, 0, st>>>(P.partial, g.S, g.ntile, g.TJ, M, N, G, ldg);
   VR_CHECK_LAUNCH();
@@ -582,7 +457,7 @@ static size_t xgemm_ws(int64_t M, int64_t N, int64_t K) {
   if (M <= 0 || N <= 0) return 256;
   const XGeom g = x_geometry(M, N, K, 1, 16);
   Carver c(nullptr);
-  c.take<double>((size_t)g.S * g.ntile * XT * XT);
+  c.take<double>((size_t)g.S * g.ntile * T64 * T64);
   return c.bytes();
 }
 
@@ -613,8 +488,8 @@ static FoldsLayout folds_layout(void* ws, int64_t p, int64_t q, int64_t k, int64
   L.eig = c.take<char>(L.eig_bytes);
   // the score products of every fold (nt <= max_test rows): S <= ceil(4 CUs / ntile), so a
   // launch's S ntile partial tiles number at most 4 CUs + ntile, ntile largest at max_test
-  const int64_t tmax = ((std::max<int64_t>(max_test, 1) + XT - 1) / XT) * ((std::max<int64_t>(k, 1) + XT - 1) / XT);
-  L.gemm_bytes = (size_t)(4LL * num_cus() + tmax) * XT * XT * sizeof(double) + 256;
+  const int64_t tmax = ((std::max<int64_t>(max_test, 1) + T64 - 1) / T64) * ((std::max<int64_t>(k, 1) + T64 - 1) / T64);
+  L.gemm_bytes = (size_t)(4LL * num_cus() + tmax) * T64 * T64 * sizeof(double) + 256;
   L.gemm = c.take<char>(L.gemm_bytes);
   L.bytes = c.bytes();
   return L;
@@ -685,8 +560,8 @@ static FoldsSvdLayout folds_svd_layout(void* ws, int64_t p, int64_t q, int64_t k
   L.svd_bytes = vr_svd_jacobi_workspace(nr, p, q);
   L.svd = c.take<char>(L.svd_bytes);
   // as folds_layout: a score product's partial tiles number at most 4 CUs + ntile
-  const int64_t tmax = ((std::max<int64_t>(max_test, 1) + XT - 1) / XT) * ((kk + XT - 1) / XT);
-  L.gemm_bytes = (size_t)(4LL * num_cus() + tmax) * XT * XT * sizeof(double) + 256;
+  const int64_t tmax = ((std::max<int64_t>(max_test, 1) + T64 - 1) / T64) * ((kk + T64 - 1) / T64);
+  L.gemm_bytes = (size_t)(4LL * num_cus() + tmax) * T64 * T64 * sizeof(double) + 256;
   L.gemm = c.take<char>(L.gemm_bytes);
   L.bytes = c.bytes();
   return L;
@@ -707,7 +582,7 @@ int vr_xgemm_nt_f32(const float* A, int64_t M, int64_t K, int64_t lda, const int
   VR_REQUIRE(M >= 0 && N >= 0 && K >= 1 && lda >= K && ldb >= K && ldg >= N,
              "vr_xgemm_nt_f32: bad shape M=%lld N=%lld K=%lld lda=%lld ldb=%lld ldg=%lld", (long long)M,
              (long long)N, (long long)K, (long long)lda, (long long)ldb, (long long)ldg);
-  VR_REQUIRE(M <= INT32_MAX && N <= INT32_MAX && ((M + XT - 1) / XT) * ((N + XT - 1) / XT) <= (1 << 24),
+  VR_REQUIRE(M <= INT32_MAX && N <= INT32_MAX && ((M + T64 - 1) / T64) * ((N + T64 - 1) / T64) <= (1 << 24),
              "vr_xgemm_nt_f32: M=%lld N=%lld too large", (long long)M, (long long)N);
   if (M == 0 || N == 0) return VR_OK;
   VR_REQUIRE(A != nullptr && B != nullptr && G != nullptr, "vr_xgemm_nt_f32: null pointer");
@@ -727,7 +602,7 @@ size_t vr_xcov_segments_workspace(int64_t p, int64_t q, int64_t F, int64_t max_s
   if (p <= 0 || q <= 0 || F <= 0) return 256;
   const XGeom g = x_geometry(p, q, max_seg, F, 4);
   Carver c(nullptr);
-  c.take<double>((size_t)F * g.S * g.ntile * XT * XT);
+  c.take<double>((size_t)F * g.S * g.ntile * T64 * T64);
   return c.bytes();
 }
 
@@ -739,7 +614,7 @@ int vr_xcov_segments_f32(const float* X, int64_t ldx, const float* Y, int64_t ld
   VR_REQUIRE(p >= 1 && q >= 1 && ldx >= p && ldy >= q, "vr_xcov_segments_f32: bad shape p=%lld q=%lld",
              (long long)p, (long long)q);
   VR_REQUIRE(seg_ok(seg, F) && F <= 65535, "vr_xcov_segments_f32: bad segments");
-  VR_REQUIRE(((p + XT - 1) / XT) * ((q + XT - 1) / XT) <= (1 << 20), "vr_xcov_segments_f32: p, q too large");
+  VR_REQUIRE(((p + T64 - 1) / T64) * ((q + T64 - 1) / T64) <= (1 << 20), "vr_xcov_segments_f32: p, q too large");
   VR_REQUIRE(S != nullptr && mean_x != nullptr && mean_y != nullptr && (seg[F] == 0 || (X != nullptr && Y != nullptr)),
              "vr_xcov_segments_f32: null pointer");
   const int64_t max_seg = seg_max(seg, F);
@@ -750,7 +625,7 @@ int vr_xcov_segments_f32(const float* X, int64_t ldx, const float* Y, int64_t ld
   hipStream_t st = as_stream(stream);
   const XGeom g = x_geometry(p, q, max_seg, F, 4);
   Carver c(ws);
-  double* partial = c.take<double>((size_t)F * g.S * g.ntile * XT * XT);
+  double* partial = c.take<double>((size_t)F * g.S * g.ntile * T64 * T64);
   XcovParams P;
   P.X = X;
   P.Y = Y;
@@ -771,8 +646,8 @@ int vr_xcov_segments_f32(const float* X, int64_t ldx, const float* Y, int64_t ld
   for (int64_t f = 0; f < F; ++f) {
     P.k0 = seg[f];
     P.k1 = seg[f + 1];
-    P.partial = partial + f * (int64_t)g.S * g.ntile * XT * XT;
-    k_xcov<<<(unsigned)(g.ntile * g.S), X_THREADS, 0, st>>>(P);
+    P.partial = partial + f * (int64_t)g.S * g.ntile * T64 * T64;
+    k_xcov<<<(unsigned)(g.ntile * g.S), T64_THREADS, 0, st>>>(P);
     VR_CHECK_LAUNCH();
     if (stats != nullptr) {
       double* sum = stats + (f * 2 + 0) * m;
