@@ -467,6 +467,51 @@ int vr_dot_u64(const uint64_t* a, const uint64_t* b, int64_t m, uint64_t* out, v
                size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------
+ * Mantel permutation test of two RDMs (csrc/mantel.hip): replaces the loop
+ *     for perm in perms: compute_rdm_correlation(A[perm][:, perm], B, correlation=...)
+ * (rsa.py:96-129 once per permutation, with one n x n gather each). A joint row/column
+ * permutation maps unordered pairs to unordered pairs one-to-one, so the triangle's mean,
+ * variance and full-triangle midranks do not depend on it: per permutation only the sum over
+ * pairs of A[perm i, perm j] * B[i, j] is new, and the permuted matrix is never formed.
+ * perms [dev] (n_perms, n) int32; every row MUST be a permutation of 0..n-1: the kernels stay
+ * inside their buffers whatever it holds, but the sums of a row that is not one mean nothing
+ * (the Python wrapper rejects such rows on the host before any launch). A result depends on its
+ * own permutation alone: not on n_perms, nor on the other rows of perms; the same call twice is
+ * bit-identical (fixed-order sums, no atomics). n <= 65535 (VR_EINVAL above: doubled midranks
+ * up to n(n-1) must fit 32 bits). lds_cols: the most entries of a matrix row a workgroup holds
+ * in LDS at once, 0 (the default, 36864 = 144 KiB) or 64 .. 36864; longer rows are walked in
+ * chunks of lds_cols, each streaming the permuted row again. n_perms = 0 writes nothing.
+ * -------------------------------------------------------------------------- */
+/* Y [dev] (n, n) u32, leading dimension ldy >= n, symmetric: Y[i][j] = Y[j][i] = the doubled
+ * midrank (2 .. 2M, M = n(n-1)/2; average ranks for ties) of A[min(i,j)][max(i,j)] among A's
+ * strict upper triangle, diagonal 0. Only A's strict upper triangle is read. tie [dev] the term
+ * sum (t^3 - t) over tie groups as u128 {lo, hi}; nan_flag [dev] one u32, non-zero if the
+ * triangle holds a NaN (the ranks then follow the key order and mean nothing to scipy). Key order
+ * and tie groups are vr_f32_sort_keys's (-0.0 == +0.0). The radix sort and midrank kernels of
+ * vr_spearman_full_f32's sort form. */
+size_t vr_triu_midranks_workspace(int64_t n);
+int vr_triu_midranks_u32(const float* A, int64_t n, int64_t ld, uint32_t* Y, int64_t ldy, uint64_t* tie,
+                         uint32_t* nan_flag, void* ws, size_t ws_bytes, void* stream);
+/* Pearson: scores [dev] n_perms doubles, scores[p] = clamp(S_p / sqrt(SS_a SS_b), -1, 1) with
+ * S_p = sum over i < j of (A[perm i, perm j] - mean_a)(B[i, j] - mean_b) in fp64; the means and
+ * SS come from the two fixed-order passes of vr_pearson_triu_f32. Only the strict upper
+ * triangles of A and B are read ([min, max] of each pair): the diagonal and the lower triangle
+ * may hold anything. NaN in every score for n(n-1)/2 < 2, a constant triangle, or a non-finite
+ * value in either strict upper triangle (vr_pearson_triu_f32's cases). */
+size_t vr_mantel_pearson_workspace(int64_t n, int64_t n_perms);
+int vr_mantel_pearson_f32(const float* A, const float* B, int64_t n, int64_t ld, const int32_t* perms,
+                          int64_t n_perms, int64_t lds_cols, double* scores, void* ws, size_t ws_bytes,
+                          void* stream);
+/* Spearman: YA, YB [dev] two rank matrices as vr_triu_midranks_u32 writes them (symmetric,
+ * zero diagonal, both with leading dimension ld). sums [dev] n_perms x u128 {lo, hi}:
+ * sums[p] = sum over i < j of YA[perm i, perm j] * YB[i, j], exact integers, no floating point
+ * and so no NaN rule (the caller turns a nan_flag into NaN scores). */
+size_t vr_mantel_ranks_workspace(int64_t n, int64_t n_perms);
+int vr_mantel_ranks_u32(const uint32_t* YA, const uint32_t* YB, int64_t n, int64_t ld, const int32_t* perms,
+                        int64_t n_perms, int64_t lds_cols, uint64_t* sums, void* ws, size_t ws_bytes,
+                        void* stream);
+
+/* ------------------------------------------------------------------------------
  * Multi-GPU RDM pieces (stimulus-sharded rows); replace the
  * block-distributed use of vr_rdm_pearson_tiles_f32 + a sum all-reduce:
  *  - each rank splits its own rows (row stats + centred bf16 hi/lo plane records);

@@ -212,6 +212,18 @@ _PROTOTYPES = {
     "vr_midranks_sorted": (ctypes.c_int, [_vp, _c_i64, ctypes.c_uint64, _vp, _vp, _vp, _c_sz, _vp]),
     "vr_dot_u64_workspace": (_c_sz, []),
     "vr_dot_u64": (ctypes.c_int, [_vp, _vp, _c_i64, _vp, _vp, _c_sz, _vp]),
+    "vr_triu_midranks_workspace": (_c_sz, [_c_i64]),
+    "vr_triu_midranks_u32": (ctypes.c_int, [_vp, _c_i64, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _c_sz, _vp]),
+    "vr_mantel_pearson_workspace": (_c_sz, [_c_i64, _c_i64]),
+    "vr_mantel_pearson_f32": (
+        ctypes.c_int,
+        [_vp, _vp, _c_i64, _c_i64, _vp, _c_i64, _c_i64, _vp, _vp, _c_sz, _vp],
+    ),
+    "vr_mantel_ranks_workspace": (_c_sz, [_c_i64, _c_i64]),
+    "vr_mantel_ranks_u32": (
+        ctypes.c_int,
+        [_vp, _vp, _c_i64, _c_i64, _vp, _c_i64, _c_i64, _vp, _vp, _c_sz, _vp],
+    ),
     "vr_rdm_plane_rows": (_c_i64, [_c_i64]),
     "vr_rdm_plane_row_bytes": (_c_sz, [_c_i64]),
     "vr_rdm_split_rows_f32": (

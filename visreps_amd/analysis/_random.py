@@ -14,7 +14,7 @@ import numpy as np
 
 from .._lib import check, lib
 
-__all__ = ["LegacyRandomState", "bootstrap_indices", "draw_bootstrap_indices"]
+__all__ = ["LegacyRandomState", "bootstrap_indices", "draw_bootstrap_indices", "permutation_indices"]
 
 
 class LegacyRandomState:
@@ -52,6 +52,21 @@ class LegacyRandomState:
         out = np.empty(int(count), dtype=np.uint32)
         check(lib().vr_rng_random_u32(self._state, int(count), out.ctypes.data), "vr_rng_random_u32")
         return out
+
+
+def permutation_indices(seed: int, n: int, n_permutations: int) -> np.ndarray:
+    """The label permutations of a Mantel test as an int32 (n_permutations + 1, n) array: row 0
+    the identity (the observed statistic), rows 1.. ``rs.permutation(n)`` drawn in sequence from
+    one ``rs = RandomState(seed)``, bit-exact with numpy."""
+    n, n_permutations = int(n), int(n_permutations)
+    if n < 0 or n_permutations < 0:
+        raise ValueError("n and n_permutations must be non-negative")
+    rng = LegacyRandomState(seed)
+    out = np.empty((n_permutations + 1, n), dtype=np.int32)
+    out[0] = np.arange(n, dtype=np.int32)
+    for i in range(1, n_permutations + 1):
+        check(lib().vr_rng_permutation(rng._state, n, out[i].ctypes.data), "vr_rng_permutation")
+    return out
 
 
 def draw_bootstrap_indices(seed: int, n: int, k: int, n_draws: int) -> np.ndarray:

@@ -28,7 +28,8 @@ import torch
 
 from .._lib import check, lib, stream_of, workspace
 from ..utils import rprint
-from ._random import LegacyRandomState, bootstrap_indices
+from ._random import LegacyRandomState, bootstrap_indices, permutation_indices
+from .distributed_spearman import _rho_from_sums
 
 if TYPE_CHECKING:  # pragma: no cover
     from .alignment import AlignmentData
@@ -48,6 +49,9 @@ __all__ = [
     "bootstrap_pearson",
     "bootstrap_full",
     "spearman_full",
+    "permutation_indices",
+    "mantel_scores",
+    "permutation_test",
     "percentile",
     "_rank",
     "_concept_average_exact",
@@ -684,6 +688,179 @@ def spearman_full(rdm1: torch.Tensor, rdm2: torch.Tensor) -> float:
 
 
 # -----------------------------------------------------------------------------
+# Mantel permutation test: p-values of an RDM comparison
+# -----------------------------------------------------------------------------
+MANTEL_MAX_N = 65535        # doubled midranks up to n(n-1) must fit 32 bits
+_MANTEL_LDS_COLS = (64, 36864)  # lds_cols: 0 (the default, the upper end) or within these
+
+
+def _validate_permutations(perms, n: int) -> np.ndarray:
+    """perms as a contiguous int32 (P, n) host array whose every row is a permutation of
+    0..n-1; ValueError otherwise. Runs on the host before any launch: the kernels take the
+    rows as permutations."""
+    if isinstance(perms, torch.Tensor):
+        perms = perms.detach().cpu().numpy()
+    p = np.asarray(perms)
+    if p.ndim != 2 or p.shape[1] != n:
+        raise ValueError(f"perms must be (n_permutations, {n}): got shape {p.shape}")
+    if p.dtype.kind not in "iu":
+        raise ValueError("perms must hold integers")
+    if p.size:
+        lo, hi = int(p.min()), int(p.max())
+        if lo < 0 or hi >= n:
+            raise ValueError(f"perms must lie in [0, {n}): found {lo if lo < 0 else hi}")
+        seen = np.zeros(p.shape, dtype=bool)
+        np.put_along_axis(seen, p.astype(np.int64), True, axis=1)
+        bad = np.flatnonzero(~seen.all(axis=1))
+        if bad.size:
+            raise ValueError(f"row {int(bad[0])} of perms is not a permutation of 0..{n - 1}")
+    out = np.ascontiguousarray(p, dtype=np.int32)
+    return out if out.flags.writeable else out.copy()  # torch.from_numpy wants a writable array
+
+
+def _mantel_inputs(rdm1, rdm2, perms, lds_cols: int):
+    dev = _device_for(rdm1, rdm2)
+    a, b = _as_device_f32(rdm1, dev), _as_device_f32(rdm2, dev)
+    if a.shape != b.shape or a.ndim != 2 or a.size(0) != a.size(1):
+        raise ValueError("RDMs must share the same square 2-D shape")
+    if a.stride(0) != b.stride(0):
+        a, b = a.contiguous(), b.contiguous()
+    n = int(a.size(0))
+    if n > MANTEL_MAX_N:
+        raise ValueError(f"the permutation test supports n <= {MANTEL_MAX_N} stimuli: got {n}")
+    lds_cols = int(lds_cols)
+    if lds_cols != 0 and not _MANTEL_LDS_COLS[0] <= lds_cols <= _MANTEL_LDS_COLS[1]:
+        raise ValueError(f"lds_cols must be 0 or in [{_MANTEL_LDS_COLS[0]}, {_MANTEL_LDS_COLS[1]}]: got {lds_cols}")
+    perms_t = torch.from_numpy(_validate_permutations(perms, n)).to(dev)
+    return dev, a, b, n, perms_t, lds_cols
+
+
+def _u128s(t: torch.Tensor) -> List[int]:
+    """(k, 2) int64 {lo, hi} words -> Python ints."""
+    return [(int(lo) & 0xFFFFFFFFFFFFFFFF) | ((int(hi) & 0xFFFFFFFFFFFFFFFF) << 64) for lo, hi in t.cpu().tolist()]
+
+
+def _rank_matrix(a: torch.Tensor) -> Tuple[torch.Tensor, int, bool]:
+    """(Y, tie, has_nan) of one RDM's strict upper triangle (vr_triu_midranks_u32): Y the
+    symmetric (n, n) matrix of doubled midranks (u32 bit patterns in int32, zero diagonal)."""
+    dev, n = a.device, int(a.size(0))
+    y = torch.empty((n, n), dtype=torch.int32, device=dev)
+    tie = torch.zeros((1, 2), dtype=torch.int64, device=dev)
+    nan = torch.zeros(1, dtype=torch.int32, device=dev)
+    L = lib()
+    ws = workspace.get(dev, L.vr_triu_midranks_workspace(n), "mantel_rank")
+    with torch.cuda.device(dev):
+        check(L.vr_triu_midranks_u32(_ptr(a), n, a.stride(0) if n else 0, _ptr(y), n, _ptr(tie), _ptr(nan),
+                                     _ptr(ws), ws.numel(), stream_of(dev)), "vr_triu_midranks_u32")
+    return y, _u128s(tie)[0], bool(int(nan.item()))
+
+
+def _mantel_rank_sums(rdm1, rdm2, perms, *, lds_cols: int = 0):
+    """The exact integers behind the Spearman permutation scores: (sums, ta, tb, M, has_nan)
+    with sums[p] = sum over i < j of yA[perm_p i, perm_p j] * yB[i, j] over the doubled midranks
+    of the two triangles (Python ints), ta / tb the tie terms, M the number of pairs."""
+    dev, a, b, n, perms_t, lds_cols = _mantel_inputs(rdm1, rdm2, perms, lds_cols)
+    P, M = int(perms_t.size(0)), n * (n - 1) // 2
+    if M < 2:  # no statistic: scipy's NaN for fewer than two pairs
+        return [0] * P, 0, 0, M, False
+    ya, ta, nan_a = _rank_matrix(a)
+    yb, tb, nan_b = _rank_matrix(b)
+    sums = torch.zeros((P, 2), dtype=torch.int64, device=dev)
+    if P:
+        L = lib()
+        ws = workspace.get(dev, L.vr_mantel_ranks_workspace(n, P), "mantel")
+        with torch.cuda.device(dev):
+            check(L.vr_mantel_ranks_u32(_ptr(ya), _ptr(yb), n, n, _ptr(perms_t), P, lds_cols, _ptr(sums),
+                                        _ptr(ws), ws.numel(), stream_of(dev)), "vr_mantel_ranks_u32")
+    return _u128s(sums), ta, tb, M, nan_a or nan_b
+
+
+def mantel_scores(rdm1: torch.Tensor, rdm2: torch.Tensor, perms, *, correlation: str = "Spearman",
+                  lds_cols: int = 0) -> torch.Tensor:
+    """compute_rdm_correlation(rdm1[p][:, p], rdm2, correlation=...) for every row p of perms,
+    as (len(perms),) float64 on the device, without forming a permuted matrix: the triangle's
+    mean, variance and full-triangle midranks do not depend on a joint row/column permutation,
+    so each row costs one pass over rdm1 (csrc/mantel.hip).
+
+    perms: (P, n) integers, every row a permutation of 0..n-1 (checked on the host; ValueError
+    otherwise). Only the strict upper triangles of the RDMs are read. Spearman scores come from
+    exact integer sums and equal spearman_full's bit for bit on the identity; Pearson scores
+    are fp64 sums in a fixed order. A score depends on its own permutation alone, not on the
+    other rows. Every score is NaN for n <= 2, a constant triangle or a NaN in either triangle
+    (for Pearson: any non-finite value). "Kendall" raises ValueError: tau has no
+    permutation-invariant moments. lds_cols bounds the row entries a workgroup keeps in LDS
+    (0: the default; longer rows are walked in chunks)."""
+    corr = correlation.lower()
+    if corr == "kendall":
+        raise ValueError("the permutation test supports 'Spearman' and 'Pearson': Kendall's tau has no "
+                         "permutation-invariant moments")
+    if corr not in ("spearman", "pearson"):
+        raise ValueError("correlation must be 'Pearson' or 'Spearman'")
+    if corr == "spearman":
+        sums, ta, tb, M, has_nan = _mantel_rank_sums(rdm1, rdm2, perms, lds_cols=lds_cols)
+        vals = [float("nan") if has_nan else _rho_from_sums(s, ta, tb, M) for s in sums]
+        return torch.tensor(vals, dtype=torch.float64, device=_device_for(rdm1, rdm2))
+    dev, a, b, n, perms_t, lds_cols = _mantel_inputs(rdm1, rdm2, perms, lds_cols)
+    P = int(perms_t.size(0))
+    scores = torch.empty(P, dtype=torch.float64, device=dev)
+    if P:
+        L = lib()
+        ws = workspace.get(dev, L.vr_mantel_pearson_workspace(n, P), "mantel")
+        with torch.cuda.device(dev):
+            check(L.vr_mantel_pearson_f32(_ptr(a), _ptr(b), n, a.stride(0) if n else 0, _ptr(perms_t), P, lds_cols,
+                                          _ptr(scores), _ptr(ws), ws.numel(), stream_of(dev)),
+                  "vr_mantel_pearson_f32")
+    return scores
+
+
+def _p_value(scores, alternative: str = "greater") -> float:
+    """Permutation p-value from scores[0] (observed) and scores[1:] (the null draws):
+    (1 + #{k >= 1: r_k >= r_0}) / (len(scores)); "less" counts r_k <= r_0 and "two-sided"
+    |r_k| >= |r_0|. NaN when the observed score is NaN."""
+    if alternative not in ("greater", "less", "two-sided"):
+        raise ValueError("alternative must be 'greater', 'less' or 'two-sided'")
+    s = np.asarray(scores, dtype=np.float64).ravel()
+    if s.size == 0:
+        raise ValueError("scores must hold the observed score")
+    r0, null = s[0], s[1:]
+    if math.isnan(r0):
+        return float("nan")
+    if alternative == "greater":
+        hits = int(np.count_nonzero(null >= r0))
+    elif alternative == "less":
+        hits = int(np.count_nonzero(null <= r0))
+    else:
+        hits = int(np.count_nonzero(np.abs(null) >= abs(r0)))
+    return (1 + hits) / (null.size + 1)
+
+
+def permutation_test(rdm1: torch.Tensor, rdm2: torch.Tensor, *, correlation: str = "Spearman",
+                     n_permutations: int = 1000, seed: int = 42,
+                     alternative: str = "greater") -> Tuple[float, float, np.ndarray]:
+    """Mantel test of the null "the stimulus labels of the two RDMs are unrelated": rdm1's rows
+    and columns are permuted together n_permutations times (permutation_indices(seed, ...): a
+    RandomState(seed) of its own) and compared with rdm2 each time. Returns (score, p_value,
+    null_scores[n_permutations])."""
+    if alternative not in ("greater", "less", "two-sided"):
+        raise ValueError("alternative must be 'greater', 'less' or 'two-sided'")
+    n = int(rdm1.shape[0])
+    perms = permutation_indices(seed, n, int(n_permutations))
+    scores = mantel_scores(rdm1, rdm2, perms, correlation=correlation).cpu().numpy()
+    return float(scores[0]), _p_value(scores, alternative), scores[1:].copy()
+
+
+def _n_permutations(cfg, method: str) -> int:
+    """cfg's opt-in "n_permutations" (0: no p-value); ValueError for a method without a test."""
+    n_perm = int(cfg.get("n_permutations", 0) or 0)
+    if n_perm < 0:
+        raise ValueError("n_permutations must be non-negative")
+    if n_perm > 0 and method not in ("spearman", "pearson"):
+        raise ValueError(f"n_permutations needs compare_method spearman or pearson, not {method!r}: "
+                         "Kendall's tau has no permutation-invariant moments")
+    return n_perm
+
+
+# -----------------------------------------------------------------------------
 # Bootstrap (evals.py:355-373) and train/test RSA (rsa.py:132-281)
 # -----------------------------------------------------------------------------
 def bootstrap_rsa(
@@ -749,6 +926,7 @@ def compute_rsa(
     optional 90 % subsample bootstrap. One RandomState(seed) feeds the n_select draw and
     then the bootstrap draws, as in the reference."""
     method = cfg.get("compare_method", "spearman").lower()
+    n_perm = _n_permutations(cfg, method)  # opt-in p-value; raises for kendall before any work
     rng = LegacyRandomState(seed)
 
     n_train = selection.neural.size(0)
@@ -864,6 +1042,10 @@ def compute_rsa(
     }
     if bootstrap_scores_list is not None:
         result["bootstrap_scores"] = bootstrap_scores_list
+    if n_perm > 0:  # its own RandomState(seed): the bootstrap stream above is untouched
+        _, result["p_value"], _ = permutation_test(test_model_rdm, test_neural_rdm, correlation=method.capitalize(),
+                                                   n_permutations=n_perm, seed=seed)
+        result["n_permutations"] = n_perm
     return [result]
 
 

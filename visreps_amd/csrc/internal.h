@@ -39,6 +39,15 @@ int radix_sort_kv(uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, uint32_t* 
 int pearson_two_pass(const float* A, const float* B, int64_t n_or_k, int64_t ld, const int32_t* idx,
                      double* out, double* part, double* mu, hipStream_t st);
 
+// After the call part still holds the second pass's per-row sums, 5 doubles per row:
+// [.., .., sum dx dy, sum dx dx, sum dy dy] (mantel.hip re-adds the last two).
+
+// ---- symmetric copy of a strict upper triangle (mantel.hip) --------------------------
+// out (n x n, leading dimension ldo) = A's strict upper triangle mirrored, diagonal 0; 32-bit
+// entries moved as bit patterns (fp32 or u32). A's diagonal and lower triangle are not read.
+// out may be A.
+int mirror_upper_u32(const uint32_t* A, int64_t n, int64_t ld, uint32_t* out, int64_t ldo, hipStream_t st);
+
 // ---- two-pass fp64 CKA traces of two kernel matrices (cka_boot.hip) -----------------
 // idx == nullptr: the full n_or_k x n_or_k matrices; else K[idx][:, idx], L[idx][:, idx] read in
 // place. part: 5 n_or_k doubles, mu: 2 doubles. out: n_out doubles, 1 (the CKA) or 4 (CKA,

@@ -1127,6 +1127,57 @@ int vr_key_table_midranks(const uint32_t* keys, int64_t m, uint32_t kmin, uint32
   return VR_OK;
 }
 
+// ---------------------------------------------------------------------------------
+// Rank matrix of one RDM (the Mantel permutation test, mantel.hip): the sort form's midranks
+// of the strict upper triangle, laid out as a symmetric n x n matrix
+// ---------------------------------------------------------------------------------
+// grid (column blocks, row slots) as k_full_keys: the upper triangle of Y from y[t]
+__global__ void k_y_to_upper(const uint64_t* __restrict__ y, int64_t n, uint32_t* __restrict__ Y, int64_t ldy) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (int64_t a = blockIdx.y; a < n; a += gridDim.y) {
+    if (b <= a || b >= n) continue;
+    Y[a * ldy + b] = (uint32_t)y[tri_index((uint64_t)a, (uint64_t)b, (uint64_t)n)];
+  }
+}
+
+size_t vr_triu_midranks_workspace(int64_t n) {
+  if (n < 2) return 256;
+  Carver c(nullptr);
+  full_layout(c, n);
+  return c.bytes();
+}
+
+int vr_triu_midranks_u32(const float* A, int64_t n, int64_t ld, uint32_t* Y, int64_t ldy, uint64_t* tie,
+                         uint32_t* nan_flag, void* ws, size_t ws_bytes, void* stream) {
+  VR_REQUIRE(n >= 0 && ld >= n && ldy >= n && tie && nan_flag, "vr_triu_midranks_u32: bad shape n=%lld ld=%lld "
+             "ldy=%lld", (long long)n, (long long)ld, (long long)ldy);
+  VR_REQUIRE(n <= 65535, "vr_triu_midranks_u32: n=%lld > 65535 (doubled midranks up to n(n-1) must fit 32 bits)",
+             (long long)n);
+  hipStream_t st = as_stream(stream);
+  VR_CHECK_HIP(hipMemsetAsync(tie, 0, 2 * sizeof(uint64_t), st));
+  VR_CHECK_HIP(hipMemsetAsync(nan_flag, 0, sizeof(uint32_t), st));
+  if (n == 0) return VR_OK;
+  VR_REQUIRE(Y != nullptr, "vr_triu_midranks_u32: null Y");
+  if (n == 1) {
+    VR_CHECK_HIP(hipMemsetAsync(Y, 0, sizeof(uint32_t), st));
+    return VR_OK;
+  }
+  VR_REQUIRE(A && ws && ws_bytes >= vr_triu_midranks_workspace(n), "vr_triu_midranks_u32: workspace");
+  const int64_t M = pairs_of(n);
+  Carver c(ws);
+  const FullWs w = full_layout(c, n);
+  VR_TRY(full_sorted(A, n, ld, w, nan_flag, st, nullptr));
+  k_y_side<false><<<(unsigned)w.nt, RS_BS, 0, st>>>(w.keys, w.tidx, M, w.nt, w.lastp1, w.first, w.yA, w.tiepart,
+                                                    nullptr);
+  VR_CHECK_LAUNCH();
+  k_reduce_u128<<<1, FULL_BS, 0, st>>>(w.tiepart, w.nt, tie);
+  VR_CHECK_LAUNCH();
+  const dim3 grid((unsigned)((n + 255) / 256), (unsigned)std::min<int64_t>(n, 16384));
+  k_y_to_upper<<<grid, 256, 0, st>>>(w.yA, n, Y, ldy);
+  VR_CHECK_LAUNCH();
+  return mirror_upper_u32(Y, n, ldy, Y, ldy, st);  // the lower triangle and a zero diagonal, in place
+}
+
 size_t vr_dot_u64_workspace(void) { return (size_t)full_grid() * 2 * sizeof(uint64_t) + 256; }
 
 int vr_dot_u64(const uint64_t* a, const uint64_t* b, int64_t m, uint64_t* out, void* ws, size_t ws_bytes,

@@ -47,8 +47,8 @@ import sqlite3
 from .analysis.alignment import (AlignmentData, _align_stimulus_level, compute_traintest_alignment,
                                  prepare_concept_alignment, prepare_traintest_alignment)
 from .analysis.reconstruct_from_pcs import reconstruct_from_pcs
-from .analysis.rsa import (RankPlan, _concept_average_exact, bootstrap_rsa, compute_rdm,
-                           compute_rdm_correlation)
+from .analysis.rsa import (RankPlan, _concept_average_exact, _n_permutations, bootstrap_rsa, compute_rdm,
+                           compute_rdm_correlation, permutation_test)
 from .analysis._random import LegacyRandomState
 from .dataloaders.neural import (_make_loader, load_nsd_synthetic_test_data, load_synthetic_data,
                                  load_things_synthetic, load_tvsd_synthetic)
@@ -150,6 +150,7 @@ def _eval_rsa(cfg, model, acts, ids, all_data, subjects, regions, dev, verbose):
     method = str(cfg.get("compare_method", "spearman")).lower()
     bootstrap = cfg.get("bootstrap", False)
     n_bootstrap = int(cfg.get("n_bootstrap", 1000))
+    n_perm = _n_permutations(cfg, method)  # opt-in p-values; raises for kendall before any work
     n_select = cfg.get("n_select", 1000)
     neural = all_data["neural"]
     shared_test_ids = all_data["shared_test_ids"]
@@ -212,7 +213,7 @@ def _eval_rsa(cfg, model, acts, ids, all_data, subjects, regions, dev, verbose):
             neural_tensor = torch.as_tensor(np.stack(responses).squeeze(), dtype=torch.float32)
             neural_rdm = compute_rdm(neural_tensor.to(dev))
             result = _score(best_layer, model_rdms, model_plans, neural_rdm, method, bootstrap,
-                            n_bootstrap, subj, per_region_scores[region][subj])
+                            n_bootstrap, subj, per_region_scores[region][subj], n_permutations=n_perm)
             if cfg.get("log_expdata"):
                 save_results(pd.DataFrame([result]), cfg.merge({"subject_idx": subj, "region": region}))
             all_results.append(result)
@@ -220,9 +221,12 @@ def _eval_rsa(cfg, model, acts, ids, all_data, subjects, regions, dev, verbose):
 
 
 def _score(best_layer, model_rdms, model_plans, neural_rdm, method, bootstrap, n_bootstrap, subj,
-           selection_scores) -> dict:
+           selection_scores, n_permutations: int = 0) -> dict:
     """Point estimate + optional bootstrap of one (region, subject) (evals.py:346-392):
-    the model RDM's rank plan is built once per layer and reused across subjects."""
+    the model RDM's rank plan is built once per layer and reused across subjects.
+    n_permutations > 0 (cfg's opt-in "n_permutations") adds the Mantel test's p_value, drawn
+    from a RandomState(42) of its own; the record is otherwise unchanged."""
+    n_permutations = _n_permutations({"n_permutations": n_permutations}, method)
     ci_low = ci_high = None
     boot_list = None
     if bootstrap and method in ("spearman", "kendall"):
@@ -254,6 +258,11 @@ def _score(best_layer, model_rdms, model_plans, neural_rdm, method, bootstrap, n
     }
     if boot_list is not None:
         result["bootstrap_scores"] = boot_list
+    if n_permutations > 0:
+        _, result["p_value"], _ = permutation_test(model_rdms[best_layer], neural_rdm,
+                                                   correlation=method.capitalize(),
+                                                   n_permutations=n_permutations, seed=42)
+        result["n_permutations"] = n_permutations
     return result
 
 
@@ -361,6 +370,7 @@ def _eval_rsa_nsd_synthetic(cfg, subjects, regions, dev, verbose):
     method = str(cfg.get("compare_method", "spearman")).lower()
     bootstrap = cfg.get("bootstrap", False)
     n_bootstrap = int(cfg.get("n_bootstrap", 1000))
+    n_perm = _n_permutations(cfg, method)  # opt-in p-values; raises for kendall before any work
     best_layers = _lookup_nsd_best_layers(cfg, subjects, regions)
     if verbose:
         for region in regions:
@@ -386,7 +396,7 @@ def _eval_rsa_nsd_synthetic(cfg, subjects, regions, dev, verbose):
             responses = [neural[region][subj][sid] for sid in test_ids]
             neural_rdm = compute_rdm(torch.as_tensor(np.stack(responses).squeeze(), dtype=torch.float32).to(dev))
             result = _score(best_layer, model_rdms, model_plans, neural_rdm, method, bootstrap,
-                            n_bootstrap, subj, [])
+                            n_bootstrap, subj, [], n_permutations=n_perm)
             if cfg.get("log_expdata"):
                 save_results(pd.DataFrame([result]), cfg.merge({"subject_idx": subj, "region": region}))
             all_results.append(result)
