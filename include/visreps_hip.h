@@ -405,6 +405,37 @@ int64_t vr_knn2_last_fallback_rows(void);
  * mean is zero. */
 int vr_twonn_id_f64(const double* r, int64_t n, double* out, void* stream);
 
+/* k nearest neighbours of every row, exact, 1 <= k <= 16: vr_knn2_f32's candidate pass,
+ * certificate and exact scan with the list length a parameter. X as there. r [dev] (n, k) doubles,
+ * row j the k smallest Euclidean distances from row j to the other rows (fp64 sums of the exact
+ * squared differences, then sqrt), ascending by (squared distance, index); nn [dev] (n, k) int32
+ * their rows (nullable). A row with fewer than k other rows (n - 1 < k) has NaN and -1 from slot
+ * n - 1 on; n = 0 writes nothing. vr_knn_candidates(k): the candidates C(k) >= k + 2 the fp32 pass
+ * keeps and the rerank measures per row (-1 for k outside [1, 16]); a row is proven iff all C are
+ * rows and r_k^2 + E < cut - E, every other row (and every row when n <= C + 1) is scanned
+ * against all rows. Bit-identical run to run; at k = 2 the bits of vr_knn2_f32 for n >= 3.
+ * VR_EINVAL for k outside [1, 16] and as vr_knn2_f32; VR_EWORKSPACE below
+ * vr_knn_workspace(n, d, k) (0 for a bad k). Synchronises the stream once.
+ * vr_knn_last_fallback_rows: rows of the last vr_knn_f32 call on this thread that took the scan. */
+int vr_knn_candidates(int k);
+size_t vr_knn_workspace(int64_t n, int64_t d, int k);
+int vr_knn_f32(const float* X, int64_t n, int64_t d, int64_t ldx, int k, double* r, int32_t* nn,
+               void* ws, size_t ws_bytes, void* stream);
+int64_t vr_knn_last_fallback_rows(void);
+/* Levina-Bickel maximum-likelihood dimension (MacKay and Ghahramani's form) from r [dev] (n, k),
+ * 2 <= k <= 16: a row counts iff r_1 > 0 and r_k is finite, s_i = (1 / (k - 1)) sum_{j < k}
+ * log(r_k / r_j); out [dev] 2 doubles, [1 / mean s_i, counted], added in the fixed order of
+ * vr_twonn_id_f64, whose bits it gives at k = 2. NaN when no row counts, inf when the mean is 0. */
+int vr_mle_id_f64(const double* r, int64_t n, int k, double* out, void* stream);
+/* Overlap of two neighbour lists nnA, nnB [dev] (n, k) int32 (entries -1 ignored), 1 <= k <= 16.
+ * counts [dev] n int32 (nullable): indices common to row i of both lists; totals [dev] 1 + P
+ * int64: totals[0] their sum, totals[1 + p] the sum over i of #{a in N_A(i): perm_p[a] in
+ * N_B(perm_p[i])} for row p of perms [dev] (P, n) int32, each a permutation of 0..n-1 (the
+ * overlap after B's rows are relabelled; P = 0: perms unused). Integer sums. P <= 2^18. */
+int vr_mutual_knn_i32(const int32_t* nnA, const int32_t* nnB, int64_t n, int k,
+                      const int32_t* perms, int64_t P, int32_t* counts, int64_t* totals,
+                      void* stream);
+
 /* ------------------------------------------------------------------------------
  * Phase-1 sparse random projection (extraction side).
  * Replaces torch.sparse.mm(P, flat.t()).t() (visreps/models/utils.py:334-336) with P the

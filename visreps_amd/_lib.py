@@ -118,6 +118,12 @@ _PROTOTYPES = {
     "vr_knn2_f32": (ctypes.c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _c_sz, _vp]),
     "vr_knn2_last_fallback_rows": (_c_i64, []),
     "vr_twonn_id_f64": (ctypes.c_int, [_vp, _c_i64, _vp, _vp]),
+    "vr_knn_candidates": (ctypes.c_int, [ctypes.c_int]),
+    "vr_knn_workspace": (_c_sz, [_c_i64, _c_i64, ctypes.c_int]),
+    "vr_knn_f32": (ctypes.c_int, [_vp, _c_i64, _c_i64, _c_i64, ctypes.c_int, _vp, _vp, _vp, _c_sz, _vp]),
+    "vr_knn_last_fallback_rows": (_c_i64, []),
+    "vr_mle_id_f64": (ctypes.c_int, [_vp, _c_i64, ctypes.c_int, _vp, _vp]),
+    "vr_mutual_knn_i32": (ctypes.c_int, [_vp, _vp, _c_i64, ctypes.c_int, _vp, _c_i64, _vp, _vp, _vp]),
     "vr_bootstrap_workspace": (_c_sz, [_c_i64]),
     "vr_bootstrap_spearman_plans": (
         ctypes.c_int,

@@ -4,7 +4,9 @@ analysis/compute_twoNN_ID.py with the nearest-neighbour search on the device.
   nearest2             the two nearest other rows of every row, exact (vr_knn2_f32)
   twoNN_id             ID = 1 / mean log(r2 / r1) on the full set and on random 1/k subsamples
   intrinsic_dim_layer  ID at k = 1 and the largest relative deviation over the subsamples, in percent
-  process_file         every conv* / fc* array of an .npz -> rows appended to a CSV next to it
+  process_file         every conv* / fc* array of an .npz -> rows appended to a CSV next to it;
+                       estimator="mle" (CLI --estimator mle --k K) swaps Two-NN for the k-neighbour
+                       maximum-likelihood estimate of analysis/neighbors.py
 
 The search is an fp32-MFMA candidate pass with a certificate and an exact fp64 scan where the
 certificate cannot hold (csrc/knn.hip), so r1 and r2 are the distances of the float32 rows
@@ -17,6 +19,8 @@ from __future__ import annotations
 
 import argparse
 import csv
+import functools
+import inspect
 import os
 import re
 
@@ -26,7 +30,8 @@ import torch
 from .._lib import check, lib, stream_of, workspace
 from .rsa import _device_for, _ptr
 
-__all__ = ["nearest2", "twoNN_id", "intrinsic_dim_layer", "process_file", "parse_decimate", "main"]
+__all__ = ["nearest2", "twoNN_id", "intrinsic_dim_layer", "process_file", "parse_decimate", "build_parser", "main",
+           "ESTIMATORS"]
 
 
 def _rows_f32(X, dev: torch.device | None = None) -> torch.Tensor:
@@ -119,11 +124,22 @@ def intrinsic_dim_layer(mat, decimate, n_jobs) -> tuple[float, float]:
 _COLUMNS = ("Epoch", "Layer", "Intrinsic_Dimensionality", "Max_Variation_%")
 
 
-def process_file(path: str, decimate, n_jobs: int, csv_name: str = "twoNN_intrinsic_dimensionality.csv"):
-    """One CSV row per conv* / fc* array of the .npz at path (1-D arrays as one column, arrays
-    of more than two dimensions flattened per row), layers with a NaN ID left out; appended to
-    csv_name in the file's directory, the header written when the CSV is new. The epoch is read
-    from "_epoch_<digits>" in the path ("NA" without it)."""
+_CSV_NAMES = {"twonn": "twoNN_intrinsic_dimensionality.csv", "mle": "mle_intrinsic_dimensionality.csv"}
+ESTIMATORS = tuple(_CSV_NAMES)
+
+
+def _mle_dim_layer(mat, decimate, k: int) -> tuple[float, float]:
+    """intrinsic_dim_layer with mle_id(mat, k, decimate) as the estimate."""
+    from .neighbors import mle_id
+
+    id1, by_q = mle_id(mat, k, decimate)
+    if np.isnan(id1):
+        return np.nan, np.nan
+    spread = [abs(v - id1) / id1 for q, v in by_q.items() if q > 1 and np.isfinite(v)]
+    return id1, (100 * max(spread) if spread else 0.0)
+
+
+def _write_layers(path: str, csv_name: str, layer_fn):
     with np.load(path, allow_pickle=True) as data:
         layers = [name for name in data.files if name.startswith(("conv", "fc"))]
         if not layers:
@@ -138,7 +154,7 @@ def process_file(path: str, decimate, n_jobs: int, csv_name: str = "twoNN_intrin
                 arr = arr[:, None]
             elif arr.ndim > 2:
                 arr = arr.reshape(arr.shape[0], -1)
-            id1, var = intrinsic_dim_layer(arr, decimate, n_jobs)
+            id1, var = layer_fn(arr)
             if np.isnan(id1):
                 continue
             rows.append(dict(zip(_COLUMNS, (epoch, name, f"{id1:.4f}", f"{var:.1f}"))))
@@ -154,19 +170,68 @@ def process_file(path: str, decimate, n_jobs: int, csv_name: str = "twoNN_intrin
         w.writerows(rows)
 
 
+def process_file(path: str, decimate, n_jobs: int, csv_name: str = "twoNN_intrinsic_dimensionality.csv"):
+    """One CSV row per conv* / fc* array of the .npz at path (1-D arrays as one column, arrays
+    of more than two dimensions flattened per row), layers with a NaN ID left out; appended to
+    csv_name in the file's directory, the header written when the CSV is new. The epoch is read
+    from "_epoch_<digits>" in the path ("NA" without it).
+
+    Two keyword-only options beyond the reference's parameters: estimator ("twonn", the default,
+    or "mle") and k (the neighbours of "mle", 2 .. 16, default 10). "mle" writes the same columns
+    from mle_id(layer, k, decimate) and, unless csv_name is given, to
+    mle_intrinsic_dimensionality.csv."""
+    return _write_layers(path, csv_name, lambda arr: intrinsic_dim_layer(arr, decimate, n_jobs))
+
+
+def _with_estimator(plain):
+    """Adds the keyword-only estimator and k to process_file. The function keeps the reference's
+    four parameters as its introspected signature (this module mirrors the reference's surface);
+    the two options are documented in its docstring."""
+    params = inspect.signature(plain)
+
+    @functools.wraps(plain)
+    def process_file(*args, estimator: str = "twonn", k: int = 10, **kwargs):
+        if estimator not in ESTIMATORS:
+            raise ValueError(f"estimator must be one of {ESTIMATORS}: got {estimator!r}")
+        if estimator == "twonn":
+            return plain(*args, **kwargs)
+        from .neighbors import _check_k
+
+        k = _check_k(k, lo=2)
+        given = params.bind(*args, **kwargs).arguments
+        csv_name = given.get("csv_name", _CSV_NAMES[estimator])
+        return _write_layers(given["path"], csv_name, lambda arr: _mle_dim_layer(arr, given["decimate"], k))
+
+    return process_file
+
+
+process_file = _with_estimator(process_file)
+
+
 def parse_decimate(text: str) -> list[int]:
     """The --decimate list: the positive integers of a comma-separated string, 1 always among them."""
     return sorted({int(t) for t in text.split(",") if int(t) > 0} | {1})
 
 
-def main(argv=None) -> None:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--input",
                     default="model_checkpoints/imagenet_cnn/cfg1/model_representations/model_reps_epoch_25.npz")
     ap.add_argument("--decimate", default="1,2,5,10")
     ap.add_argument("--n_jobs", type=int, default=-1)
-    args = ap.parse_args(argv)
-    process_file(args.input, parse_decimate(args.decimate), args.n_jobs)
+    ap.add_argument("--estimator", choices=ESTIMATORS, default="twonn",
+                    help="twonn: Facco Two-NN; mle: k-neighbour maximum likelihood (Levina-Bickel)")
+    ap.add_argument("--k", type=int, default=10, choices=range(2, 17), metavar="2..16",
+                    help="neighbours of --estimator mle")
+    return ap
+
+
+def main(argv=None) -> None:
+    args = build_parser().parse_args(argv)
+    if args.estimator == "twonn":
+        process_file(args.input, parse_decimate(args.decimate), args.n_jobs)
+    else:
+        process_file(args.input, parse_decimate(args.decimate), args.n_jobs, estimator=args.estimator, k=args.k)
 
 
 if __name__ == "__main__":

@@ -33,6 +33,15 @@
 //               k_knn_exact_merge picks the two smallest by (value, index) over the chunks.
 // k_twonn_reduce     kept = #{r1 > 0}, sum of log(r2 / r1) in a fixed order, [1 / mean, kept].
 //
+// k neighbours, 1 <= k <= 16 (vr_knn_f32): the same pass with the list length L = C + 1 a template
+// parameter of kn_insert, k_knn_cand and k_knn_merge, C(k) = 4, 12, 24 for k <= 2, 8, 16. L = 5 is
+// the two-neighbour search's code; longer lists are kept one per thread and selected from the tile
+// of s~ in LDS (see k_knn_cand). The certificate is the one below with r_k for r2 (the bound is per
+// pair and does not depend on k). The exact paths keep their k smallest as a list spread over the
+// lanes of a wave: k_knn_rerank_k, k_knn_exact_rows_k, k_knn_exact_merge_k. On top of the lists:
+// k_mle_reduce   the k-neighbour maximum-likelihood dimension, k_twonn_reduce's order and, at k = 2, bits.
+// k_mutual_knn   overlap counts of two neighbour lists, and their totals under relabellings of one.
+//
 // The bound. With u = 2^-24, A_i the exact squared norm of the staged row y_i, G_ij the exact dot
 // of staged rows and D_ij^2 the exact squared distance of the caller's rows:
 //   staging   y_ik = (x_ik - m_k)(1 + delta), |delta| <= u, so y_i - y_j = (x_i - x_j) + e_i - e_j
@@ -164,13 +173,14 @@ __global__ __launch_bounds__(256) void k_knn_amax(const double* __restrict__ a64
 }
 
 // ---- candidate pass --------------------------------------------------------------------
-// ascending list of KN_L (value, index); a new value enters only if strictly smaller than the last
-__device__ inline void kn_insert(float (&v)[KN_L], int32_t (&id)[KN_L], float s, int32_t i) {
-  if (!(s < v[KN_L - 1])) return;
-  v[KN_L - 1] = s;
-  id[KN_L - 1] = i;
+// ascending list of L (value, index); a new value enters only if strictly smaller than the last
+template <int L>
+__device__ inline void kn_insert(float (&v)[L], int32_t (&id)[L], float s, int32_t i) {
+  if (!(s < v[L - 1])) return;
+  v[L - 1] = s;
+  id[L - 1] = i;
 #pragma unroll
-  for (int q = KN_L - 1; q > 0; --q) {
+  for (int q = L - 1; q > 0; --q) {
     const bool sw = v[q] < v[q - 1];
     const float tv = v[q];
     const int32_t ti = id[q];
@@ -187,11 +197,24 @@ struct KnParams {
   const float* a32;   // n_pad norms
   int64_t n, n_pad;
   int T, S;           // row tiles, row ranges per column block
-  float* listV;       // [S][n_pad][KN_L]
+  float* listV;       // [S][n_pad][L]
   int32_t* listI;
 };
 
+// L = KN_L keeps the lists per lane (two columns each, four lanes per column), selected from the
+// accumulators in place: the form and the arithmetic of the two-neighbour search. A longer list
+// (L = 13, 25) would cost 2 L (value, index) pairs per lane and 64 copies of the insertion chain,
+// so there the tile of s~ goes through the panel buffer (free after the k loop's last barrier):
+// thread t owns column t & 127 and rows 64 (t >> 7) .. of the tile, reads them in row order and
+// keeps one list. One chain per unrolled read, L pairs per thread, two parts per column to merge.
+template <int L>
 __global__ __launch_bounds__(KN_THREADS, 2) void k_knn_cand(KnParams P) {
+  constexpr bool kLane = (L == KN_L);
+  constexpr int NLIST = kLane ? 2 : 1;   // lists per thread
+  constexpr int NPART = kLane ? 4 : 2;   // lists per column and workgroup
+  constexpr int kQUnroll = L <= 13 ? 4 : 2;  // steps of a k stage unrolled
+  static_assert(KN_T * KN_T <= 2 * 2 * KN_STAGE, "the tile of s~ must fit the panel buffer");
+  static_assert(KN_T * NPART * L * 2 <= 2 * 2 * KN_STAGE, "the lists to merge must fit the panel buffer");
   __shared__ __attribute__((aligned(16))) float lds[2 * 2 * KN_STAGE];  // [buf][A/B]
   __shared__ float an[KN_T];
   const int id = (int)xcd_remap(blockIdx.x, gridDim.x);
@@ -203,20 +226,23 @@ __global__ __launch_bounds__(KN_THREADS, 2) void k_knn_cand(KnParams P) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int wr = wid >> 1, wc = wid & 1, h = lane >> 5, l32 = lane & 31;
 
-  float lv[2][KN_L];
-  int32_t li[2][KN_L];
+  float lv[NLIST][L];
+  int32_t li[NLIST][L];
   float aj[2];
   int32_t jc[2];
 #pragma unroll
   for (int nn = 0; nn < 2; ++nn) {
     jc[nn] = (int32_t)(col0 + wc * 64 + nn * 32 + l32);  // < n_pad
     aj[nn] = P.a32[jc[nn]];
+  }
 #pragma unroll
-    for (int e = 0; e < KN_L; ++e) {
+  for (int nn = 0; nn < NLIST; ++nn)
+#pragma unroll
+    for (int e = 0; e < L; ++e) {
       lv[nn][e] = std::numeric_limits<float>::infinity();
       li[nn][e] = -1;
     }
-  }
+  const int tc = threadIdx.x & (KN_T - 1), tp = threadIdx.x >> 7;  // L > KN_L: the thread's column and half
 
   // thread t stages float4 t + 256 s of a 128 x 32 panel: row f >> 3, columns 4 (f & 7) ..
   auto load_panel = [&](int64_t r0, int64_t k, kf32x4 (&v)[4]) {
@@ -265,7 +291,8 @@ __global__ __launch_bounds__(KN_THREADS, 2) void k_knn_cand(KnParams P) {
         if (!diag) load_panel(col0, kn, gb);
       }
       // lane half h owns k in [16 h, 16 h + 16) of the stage: a fixed permutation of the sum over k
-#pragma unroll
+      // (L = 25: two steps unrolled, not four; with all four the 50 list registers spill)
+#pragma unroll kQUnroll
       for (int q = 0; q < 4; ++q) {
         kf32x4 av[2], bv[2];
 #pragma unroll
@@ -292,77 +319,102 @@ __global__ __launch_bounds__(KN_THREADS, 2) void k_knn_cand(KnParams P) {
     // C/D of the 32 x 32 MFMA: column l32, rows (r & 3) + 8 (r >> 2) + 4 h. Select per column.
     const int lbase = wr * 64 + 4 * h;
     const int32_t irow0 = (int32_t)row0, n32 = (int32_t)P.n;
+    if constexpr (kLane) {
 #pragma unroll
-    for (int nn = 0; nn < 2; ++nn)
+      for (int nn = 0; nn < 2; ++nn)
 #pragma unroll
-      for (int m = 0; m < 2; ++m)
+        for (int m = 0; m < 2; ++m)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int lr = lbase + m * 32 + (r & 3) + 8 * (r >> 2);
-          const int32_t i = irow0 + lr;  // < n_pad <= 2^20
-          const float s = __fmaf_rn(-2.f, acc[m][nn][r], __fadd_rn(an[lr], aj[nn]));
-          if (i < n32 && i != jc[nn]) kn_insert(lv[nn], li[nn], s, i);
-        }
+          for (int r = 0; r < 16; ++r) {
+            const int lr = lbase + m * 32 + (r & 3) + 8 * (r >> 2);
+            const int32_t i = irow0 + lr;  // < n_pad <= 2^20
+            const float s = __fmaf_rn(-2.f, acc[m][nn][r], __fadd_rn(an[lr], aj[nn]));
+            if (i < n32 && i != jc[nn]) kn_insert<L>(lv[nn], li[nn], s, i);
+          }
+    } else {
+      float* tile = lds;  // [row 128][column 128]: a wave stores 32 consecutive columns of two rows
+#pragma unroll
+      for (int nn = 0; nn < 2; ++nn)
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int lr = lbase + m * 32 + (r & 3) + 8 * (r >> 2);
+            tile[lr * KN_T + wc * 64 + nn * 32 + l32] =
+                __fmaf_rn(-2.f, acc[m][nn][r], __fadd_rn(an[lr], aj[nn]));
+          }
+      __syncthreads();
+      const int32_t j = (int32_t)col0 + tc;
+#pragma unroll 4
+      for (int q = 0; q < KN_T / 2; ++q) {  // a wave reads 64 consecutive columns of one row
+        const int lr = tp * (KN_T / 2) + q;
+        const int32_t i = irow0 + lr;
+        const float s = tile[lr * KN_T + tc];
+        if (i < n32 && i != j) kn_insert<L>(lv[0], li[0], s, i);
+      }
+    }
     __syncthreads();  // an and the panels are rewritten by the next tile
   }
 
-  // the four lanes of a column (wr, h) through LDS, merged in that order
-  float* lf = lds;  // [col 128][part 4][KN_L][2]
+  // the lists of a column through LDS, merged in part order: the four lanes (wr, h), or the two halves
+  float* lf = lds;  // [col 128][part NPART][L][2]
 #pragma unroll
-  for (int nn = 0; nn < 2; ++nn) {
-    const int c = wc * 64 + nn * 32 + l32;
+  for (int nn = 0; nn < NLIST; ++nn) {
+    const int c = kLane ? wc * 64 + nn * 32 + l32 : tc;
+    const int part = kLane ? wr * 2 + h : tp;
 #pragma unroll
-    for (int e = 0; e < KN_L; ++e) {
-      float* p = lf + (((c * 4) + wr * 2 + h) * KN_L + e) * 2;
+    for (int e = 0; e < L; ++e) {
+      float* p = lf + (((c * NPART) + part) * L + e) * 2;
       p[0] = lv[nn][e];
       p[1] = __int_as_float(li[nn][e]);
     }
   }
   __syncthreads();
   if (threadIdx.x < KN_T) {
-    float mv[KN_L];
-    int32_t mi[KN_L];
+    float mv[L];
+    int32_t mi[L];
 #pragma unroll
-    for (int e = 0; e < KN_L; ++e) {
+    for (int e = 0; e < L; ++e) {
       mv[e] = std::numeric_limits<float>::infinity();
       mi[e] = -1;
     }
-    for (int p = 0; p < 4; ++p)
+    for (int p = 0; p < NPART; ++p)
 #pragma unroll
-      for (int e = 0; e < KN_L; ++e) {
-        const float* q = lf + (((threadIdx.x * 4) + p) * KN_L + e) * 2;
-        kn_insert(mv, mi, q[0], __float_as_int(q[1]));
+      for (int e = 0; e < L; ++e) {
+        const float* q = lf + (((threadIdx.x * NPART) + p) * L + e) * 2;
+        kn_insert<L>(mv, mi, q[0], __float_as_int(q[1]));
       }
-    const int64_t o = ((int64_t)split * P.n_pad + col0 + threadIdx.x) * KN_L;
+    const int64_t o = ((int64_t)split * P.n_pad + col0 + threadIdx.x) * L;
 #pragma unroll
-    for (int e = 0; e < KN_L; ++e) {
+    for (int e = 0; e < L; ++e) {
       P.listV[o + e] = mv[e];
       P.listI[o + e] = mi[e];
     }
   }
 }
 
-// one thread per point: the S range lists in range order
+// one thread per point: the S range lists in range order; L - 1 candidates and the cut
+template <int L>
 __global__ __launch_bounds__(256) void k_knn_merge(const float* __restrict__ listV, const int32_t* __restrict__ listI,
                                                    int64_t n, int64_t n_pad, int S, int32_t* __restrict__ cand,
                                                    float* __restrict__ cut) {
   const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (j >= n) return;
-  float mv[KN_L];
-  int32_t mi[KN_L];
+  float mv[L];
+  int32_t mi[L];
 #pragma unroll
-  for (int e = 0; e < KN_L; ++e) {
+  for (int e = 0; e < L; ++e) {
     mv[e] = std::numeric_limits<float>::infinity();
     mi[e] = -1;
   }
   for (int s = 0; s < S; ++s) {
-    const int64_t o = ((int64_t)s * n_pad + j) * KN_L;
+    const int64_t o = ((int64_t)s * n_pad + j) * L;
 #pragma unroll
-    for (int e = 0; e < KN_L; ++e) kn_insert(mv, mi, listV[o + e], listI[o + e]);
+    for (int e = 0; e < L; ++e) kn_insert<L>(mv, mi, listV[o + e], listI[o + e]);
   }
 #pragma unroll
-  for (int e = 0; e < KN_C; ++e) cand[j * KN_C + e] = mi[e];
-  cut[j] = mv[KN_C];
+  for (int e = 0; e < L - 1; ++e) cand[j * (L - 1) + e] = mi[e];
+  cut[j] = mv[L - 1];
 }
 
 // ---- exact arithmetic ------------------------------------------------------------------
@@ -488,6 +540,138 @@ __global__ void k_knn_nan(double* __restrict__ r, int32_t* __restrict__ nn, int6
   if (nn) nn[e] = -1;
 }
 
+// ---- k neighbours: the exact paths of vr_knn_f32 ------------------------------------------
+// A sorted list of k <= KN_KMAX (value, index) spread over a wave: lane e keeps element e, lanes
+// >= k keep (inf, INT_MAX). Every value a wave handles on the exact paths is wave-uniform
+// (wave_dist2 ends with the same bits in every lane), so an insertion is one ballot and one
+// shift by a lane: no list in registers, no dynamic register index.
+constexpr int KN_KMAX = 16;
+constexpr int32_t KN_NONE = 0x7fffffff;
+
+__device__ inline void wl_insert(double& myv, int32_t& myi, double v, int32_t i, int k, int lane) {
+  const bool lt = lane < k && kn_less(v, i, myv, myi);
+  const unsigned long long m = __ballot(lt);
+  if (m == 0) return;  // uniform: not among the k smallest
+  const int pos = __ffsll(m) - 1;
+  const double pv = __shfl_up(myv, 1, 64);
+  const int32_t pi = __shfl_up(myi, 1, 64);
+  if (lane == pos) {
+    myv = v;
+    myi = i;
+  } else if (lane > pos && lane < k) {
+    myv = pv;
+    myi = pi;
+  }
+}
+
+__device__ inline void wl_write(double myv, int32_t myi, int64_t j, int k, int lane, double* __restrict__ r,
+                                int32_t* __restrict__ nn) {
+  if (lane >= k) return;
+  const bool none = myi == KN_NONE;
+  r[j * k + lane] = none ? __builtin_nan("") : sqrt(myv);
+  if (nn) nn[j * k + lane] = none ? -1 : myi;
+}
+
+// one wave per point: lane c takes the exact squared distance to candidate c (C <= 24), its rank
+// by (value, index) among the C is a count over the lanes, and ranks < k are the result. Proven
+// iff all C candidates are rows and r_k^2 + E_j < cut_j - E_j.
+__global__ __launch_bounds__(256) void k_knn_rerank_k(const float* __restrict__ X, int64_t n, int64_t d, int64_t ldx,
+                                                      const int32_t* __restrict__ cand, int C,
+                                                      const float* __restrict__ cut, const double* __restrict__ a64,
+                                                      const double* __restrict__ amax, double efac, int k,
+                                                      double* __restrict__ r, int32_t* __restrict__ nn,
+                                                      int32_t* __restrict__ fail_list,
+                                                      int32_t* __restrict__ fail_count) {
+  const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= n) return;
+  const int lane = threadIdx.x & 63;
+  double myv = std::numeric_limits<double>::infinity();
+  int32_t myi = KN_NONE;
+  bool all = true;
+  for (int c = 0; c < C; ++c) {
+    const int32_t i = cand[j * C + c];
+    if (i < 0 || i >= n) {  // uniform over the wave
+      all = false;
+      continue;
+    }
+    const double v = wave_dist2(X + j * ldx, X + (int64_t)i * ldx, d);
+    if (lane == c) {
+      myv = v;
+      myi = i;
+    }
+  }
+  int rank = 0;
+  for (int f = 0; f < C; ++f) {
+    const double wv = __shfl(myv, f, 64);
+    const int32_t wi = __shfl(myi, f, 64);
+    rank += kn_less(wv, wi, myv, myi) ? 1 : 0;
+  }
+  // a row with a missing candidate is rewritten whole by the exact scan
+  if (lane < C && rank < k) {
+    r[j * k + rank] = sqrt(myv);
+    if (nn) nn[j * k + rank] = myi == KN_NONE ? -1 : myi;
+  }
+  const unsigned long long kth = __ballot(lane < C && rank == k - 1);
+  const double vk = __shfl(myv, kth ? __ffsll(kth) - 1 : 0, 64);
+  if (lane != 0) return;
+  const double E = efac * (a64[j] + *amax);
+  const double c = (double)cut[j];
+  const bool proven = all && kth != 0 && c < std::numeric_limits<double>::infinity() && (vk + E < c - E);
+  if (!proven) fail_list[atomicAdd(fail_count, 1)] = (int32_t)j;
+}
+
+// k_knn_exact_rows for k neighbours: block (x, y) as there; the k smallest by (value, index) of
+// the chunk, ascending, go to part[(x * Q + y) * k ..] (missing ones (inf, INT_MAX)).
+__global__ __launch_bounds__(256) void k_knn_exact_rows_k(const float* __restrict__ X, int64_t n, int64_t d,
+                                                          int64_t ldx, const int32_t* __restrict__ list,
+                                                          int64_t rows_per, int k, double* __restrict__ partV,
+                                                          int32_t* __restrict__ partI) {
+  __shared__ double wv[4][KN_KMAX];
+  __shared__ int32_t wi[4][KN_KMAX];
+  const int64_t j = list ? (int64_t)list[blockIdx.x] : (int64_t)blockIdx.x;
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  double myv = std::numeric_limits<double>::infinity();
+  int32_t myi = KN_NONE;
+  if (j >= 0 && j < n) {  // uniform over the block
+    const int64_t i0 = (int64_t)blockIdx.y * rows_per, i1 = min(n, i0 + rows_per);
+    for (int64_t i = i0 + w; i < i1; i += 4)
+      if (i != j) wl_insert(myv, myi, wave_dist2(X + j * ldx, X + i * ldx, d), (int32_t)i, k, lane);
+  }
+  if (lane < k) {
+    wv[w][lane] = myv;
+    wi[w][lane] = myi;
+  }
+  __syncthreads();
+  if (w != 0) return;
+  for (int q = 1; q < 4; ++q)
+    for (int e = 0; e < k; ++e) wl_insert(myv, myi, wv[q][e], wi[q][e], k, lane);
+  if (lane < k) {
+    const int64_t o = ((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * k + lane;
+    partV[o] = myv;
+    partI[o] = myi;
+  }
+}
+
+// one wave per listed row: its Q chunks
+__global__ __launch_bounds__(256) void k_knn_exact_merge_k(const double* __restrict__ partV,
+                                                           const int32_t* __restrict__ partI, int64_t rows, int Q,
+                                                           int64_t n, const int32_t* __restrict__ list, int k,
+                                                           double* __restrict__ r, int32_t* __restrict__ nn) {
+  const int64_t x = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (x >= rows) return;
+  const int64_t j = list ? (int64_t)list[x] : x;
+  if (j < 0 || j >= n) return;
+  const int lane = threadIdx.x & 63;
+  double myv = std::numeric_limits<double>::infinity();
+  int32_t myi = KN_NONE;
+  for (int q = 0; q < Q; ++q)
+    for (int e = 0; e < k; ++e) {
+      const int64_t o = (x * Q + q) * k + e;
+      wl_insert(myv, myi, partV[o], partI[o], k, lane);
+    }
+  wl_write(myv, myi, j, k, lane, r, nn);
+}
+
 // ---- Two-NN reduction ------------------------------------------------------------------
 // thread t adds rows t, t + 256, .. in order; then the block in a fixed order
 __global__ __launch_bounds__(256) void k_twonn_reduce(const double* __restrict__ r, int64_t n, double* __restrict__ out) {
@@ -508,6 +692,72 @@ __global__ __launch_bounds__(256) void k_twonn_reduce(const double* __restrict__
   }
 }
 
+// ---- k-neighbour reductions ---------------------------------------------------------------
+// The Levina-Bickel estimator in MacKay and Ghahramani's form from r (n, k), k >= 2: a row counts
+// iff r_1 > 0 and r_k is finite, s_i = (1 / (k - 1)) sum_{j < k} log(r_k / r_j), out = [1 / mean s_i,
+// counted]. The summation order of k_twonn_reduce; at k = 2 its terms, so its bits.
+__global__ __launch_bounds__(256) void k_mle_reduce(const double* __restrict__ r, int64_t n, int k,
+                                                    double* __restrict__ out) {
+  __shared__ double red[4];
+  double s = 0.0, c = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += 256) {
+    const double r1 = r[i * k], rk = r[i * k + k - 1];
+    if (r1 > 0.0 && rk - rk == 0.0) {  // rk finite
+      double t = 0.0;
+      for (int j = 0; j < k - 1; ++j) t += log(rk / r[i * k + j]);
+      s += t / (double)(k - 1);
+      c += 1.0;
+    }
+  }
+  s = kn_block_sum(s, red);
+  c = kn_block_sum(c, red);
+  if (threadIdx.x == 0) {
+    out[0] = c > 0.0 ? 1.0 / (s / c) : __builtin_nan("");
+    out[1] = c;
+  }
+}
+
+// Overlap of two neighbour lists. Thread = row i, block y = MK_SLOTS relabellings: slot 0 the
+// identity (counts[i] and totals[0]), slot 1 + p the permutation p, where row i counts the a in
+// N_A(i) with perm[a] in N_B(perm[i]). Both lists sit in registers behind static indices (entries
+// past k are -1, which no row index equals). Integer sums: a wave tree, then one integer atomic.
+constexpr int MK_SLOTS = 8;
+
+__global__ __launch_bounds__(256) void k_mutual_knn(const int32_t* __restrict__ nnA, const int32_t* __restrict__ nnB,
+                                                    int64_t n, int k, const int32_t* __restrict__ perms,
+                                                    int64_t slots, int32_t* __restrict__ counts,
+                                                    unsigned long long* __restrict__ totals) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool valid = i < n;
+  int32_t a[KN_KMAX];
+#pragma unroll
+  for (int e = 0; e < KN_KMAX; ++e) a[e] = (valid && e < k) ? nnA[i * k + e] : -1;
+  const int64_t s0 = (int64_t)blockIdx.y * MK_SLOTS, s1 = min(slots, s0 + MK_SLOTS);
+  for (int64_t s = s0; s < s1; ++s) {
+    const int32_t* pm = s == 0 ? nullptr : perms + (s - 1) * n;
+    int cnt = 0;
+    const int64_t pi = !valid ? -1 : pm ? (int64_t)pm[i] : i;
+    if (pi >= 0 && pi < n) {
+      int32_t b[KN_KMAX];
+#pragma unroll
+      for (int e = 0; e < KN_KMAX; ++e) b[e] = e < k ? nnB[pi * k + e] : -1;
+#pragma unroll
+      for (int e = 0; e < KN_KMAX; ++e) {
+        const int32_t ae = a[e];
+        if (ae < 0 || ae >= n) continue;
+        const int32_t pa = pm ? pm[ae] : ae;
+        bool hit = false;
+#pragma unroll
+        for (int f = 0; f < KN_KMAX; ++f) hit = hit || (b[f] == pa && pa >= 0);
+        cnt += hit ? 1 : 0;
+      }
+    }
+    if (s == 0 && valid && counts) counts[i] = cnt;
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(totals + s, (unsigned long long)cnt);
+  }
+}
+
 struct KnLayout {
   int64_t n_pad, d_pad;
   int T, S, chunks;
@@ -523,11 +773,15 @@ struct KnLayout {
   float* cut;
   int32_t* fail_list;
   int32_t* fail_count;
-  Best2* xpart;  // chunk results of the exact scan
+  Best2* xpart;  // chunk results of the exact scan (two neighbours)
+  double* xpartV;  // k neighbours: [rows * Q][k]
+  int32_t* xpartI;
   size_t bytes;
 };
 
-static KnLayout kn_layout(void* ws, int64_t n, int64_t d) {
+// C candidates per row; k = 0 is the two-neighbour search (its Best2 chunk results), k >= 1 sizes
+// the chunk lists of vr_knn_f32
+static KnLayout kn_layout(void* ws, int64_t n, int64_t d, int C = KN_C, int k = 0) {
   KnLayout L;
   const int64_t nn = std::max<int64_t>(n, 1), dd = std::max<int64_t>(d, 1);
   L.n_pad = (nn + KN_T - 1) / KN_T * KN_T;
@@ -543,13 +797,21 @@ static KnLayout kn_layout(void* ws, int64_t n, int64_t d) {
   L.a64 = c.take<double>((size_t)L.n_pad);
   L.a32 = c.take<float>((size_t)L.n_pad);
   L.amax = c.take<double>(1);
-  L.listV = c.take<float>((size_t)KN_SMAX * L.n_pad * KN_L);
-  L.listI = c.take<int32_t>((size_t)KN_SMAX * L.n_pad * KN_L);
-  L.cand = c.take<int32_t>((size_t)L.n_pad * KN_C);
+  L.listV = c.take<float>((size_t)KN_SMAX * L.n_pad * (C + 1));
+  L.listI = c.take<int32_t>((size_t)KN_SMAX * L.n_pad * (C + 1));
+  L.cand = c.take<int32_t>((size_t)L.n_pad * C);
   L.cut = c.take<float>((size_t)L.n_pad);
   L.fail_list = c.take<int32_t>((size_t)L.n_pad);
   L.fail_count = c.take<int32_t>(1);
-  L.xpart = c.take<Best2>((size_t)L.n_pad + KN_XBLK);
+  L.xpart = nullptr;
+  L.xpartV = nullptr;
+  L.xpartI = nullptr;
+  if (k == 0) {
+    L.xpart = c.take<Best2>((size_t)L.n_pad + KN_XBLK);
+  } else {
+    L.xpartV = c.take<double>(((size_t)L.n_pad + KN_XBLK) * k);
+    L.xpartI = c.take<int32_t>(((size_t)L.n_pad + KN_XBLK) * k);
+  }
   L.bytes = c.bytes();
   return L;
 }
@@ -566,6 +828,52 @@ static int exact_scan(const float* X, int64_t n, int64_t d, int64_t ldx, const i
   k_knn_exact_rows<<<dim3((unsigned)rows, (unsigned)Q), 256, 0, st>>>(X, n, d, ldx, list, rows_per, Y.xpart);
   VR_CHECK_LAUNCH();
   k_knn_exact_merge<<<(unsigned)((rows + 255) / 256), 256, 0, st>>>(Y.xpart, rows, Q, n, list, r, nn);
+  VR_CHECK_LAUNCH();
+  return VR_OK;
+}
+
+static thread_local int64_t g_last_fallback_k = 0;
+
+// candidates reranked per row: C(k) >= k + 2, one k_knn_cand instantiation each
+static int knn_candidates(int k) { return k < 1 || k > KN_KMAX ? -1 : k <= 2 ? KN_C : k <= 8 ? 12 : 24; }
+
+static int exact_scan_k(const float* X, int64_t n, int64_t d, int64_t ldx, const int32_t* list, int64_t rows,
+                        const KnLayout& Y, int k, double* r, int32_t* nn, hipStream_t st) {
+  const int64_t q_max = std::min<int64_t>(256, (n + 3) / 4);
+  const int Q = (int)std::max<int64_t>(1, std::min<int64_t>(q_max, (KN_XBLK + rows - 1) / rows));
+  const int64_t rows_per = (n + Q - 1) / Q;
+  KtScope kt(KT_KNN_EXACT, (double)rows * (double)n, st);
+  k_knn_exact_rows_k<<<dim3((unsigned)rows, (unsigned)Q), 256, 0, st>>>(X, n, d, ldx, list, rows_per, k, Y.xpartV,
+                                                                       Y.xpartI);
+  VR_CHECK_LAUNCH();
+  k_knn_exact_merge_k<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(Y.xpartV, Y.xpartI, rows, Q, n, list, k, r, nn);
+  VR_CHECK_LAUNCH();
+  return VR_OK;
+}
+
+template <int L>
+static int launch_cand(const KnLayout& Y, int64_t n, hipStream_t st) {
+  {
+    KnParams P;
+    P.Y = Y.Y;
+    P.ldy = Y.d_pad;
+    P.a32 = Y.a32;
+    P.n = n;
+    P.n_pad = Y.n_pad;
+    P.T = Y.T;
+    P.S = Y.S;
+    P.listV = Y.listV;
+    P.listI = Y.listI;
+    KtScope kt(KT_KNN_CAND, 2.0 * (double)Y.n_pad * (double)Y.n_pad * (double)Y.d_pad, st);
+    k_knn_cand<L><<<(unsigned)(Y.T * Y.S), KN_THREADS, 0, st>>>(P);
+    VR_CHECK_LAUNCH();
+  }
+  return VR_OK;
+}
+
+template <int L>
+static int launch_merge(const KnLayout& Y, int64_t n, hipStream_t st) {
+  k_knn_merge<L><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(Y.listV, Y.listI, n, Y.n_pad, Y.S, Y.cand, Y.cut);
   VR_CHECK_LAUNCH();
   return VR_OK;
 }
@@ -643,14 +951,14 @@ int vr_knn2_f32(const float* X, int64_t n, int64_t d, int64_t ldx, double* r, in
     P.listI = Y.listI;
     // every tile is walked once: 2 (128)^2 d_pad FLOP each
     KtScope kt(KT_KNN_CAND, 2.0 * (double)Y.n_pad * (double)Y.n_pad * (double)Y.d_pad, st);
-    k_knn_cand<<<(unsigned)(Y.T * Y.S), KN_THREADS, 0, st>>>(P);
+    k_knn_cand<KN_L><<<(unsigned)(Y.T * Y.S), KN_THREADS, 0, st>>>(P);
     VR_CHECK_LAUNCH();
   }
   const double u = 0x1p-24, du = (double)d * u;
   const double efac = du < 0.5 ? 1.001 * (du / (1.0 - du) + 9.0 * u) : std::numeric_limits<double>::infinity();
   {
     KtScope kt(KT_KNN_RERANK, (double)n * KN_C, st);
-    k_knn_merge<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(Y.listV, Y.listI, n, Y.n_pad, Y.S, Y.cand, Y.cut);
+    k_knn_merge<KN_L><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(Y.listV, Y.listI, n, Y.n_pad, Y.S, Y.cand, Y.cut);
     VR_CHECK_LAUNCH();
     k_knn_rerank<<<(unsigned)((n + 3) / 4), 256, 0, st>>>(X, n, d, ldx, Y.cand, Y.cut, Y.a64, Y.amax, efac, r, nn,
                                                          Y.fail_list, Y.fail_count);
@@ -674,6 +982,100 @@ int vr_twonn_id_f64(const double* r, int64_t n, double* out, void* stream) {
   VR_REQUIRE(n >= 0, "vr_twonn_id_f64: bad n=%lld", (long long)n);
   VR_REQUIRE(out != nullptr && (n == 0 || r != nullptr), "vr_twonn_id_f64: null pointer");
   k_twonn_reduce<<<1, 256, 0, as_stream(stream)>>>(r, n, out);
+  VR_CHECK_LAUNCH();
+  return VR_OK;
+}
+
+int vr_knn_candidates(int k) { return knn_candidates(k); }
+
+size_t vr_knn_workspace(int64_t n, int64_t d, int k) {
+  const int C = knn_candidates(k);
+  if (C < 0) return 0;
+  return kn_layout(nullptr, std::min<int64_t>(std::max<int64_t>(n, 0), KN_NMAX), d, C, k).bytes;
+}
+
+int64_t vr_knn_last_fallback_rows(void) { return g_last_fallback_k; }
+
+int vr_knn_f32(const float* X, int64_t n, int64_t d, int64_t ldx, int k, double* r, int32_t* nn, void* ws,
+               size_t ws_bytes, void* stream) {
+  clear_error();
+  const int C = knn_candidates(k);
+  VR_REQUIRE(C > 0, "vr_knn_f32: k=%d outside [1, %d]", k, KN_KMAX);
+  VR_REQUIRE(n >= 0 && n <= KN_NMAX && d >= 1 && ldx >= d, "vr_knn_f32: bad shape n=%lld d=%lld ldx=%lld",
+             (long long)n, (long long)d, (long long)ldx);
+  VR_REQUIRE(X != nullptr && r != nullptr, "vr_knn_f32: null pointer");
+  const size_t need = kn_layout(nullptr, n, d, C, k).bytes;
+  if (ws_bytes < need || ws == nullptr) {
+    set_error("vr_knn_f32: workspace %zu < %zu", ws_bytes, need);
+    return VR_EWORKSPACE;
+  }
+  g_last_fallback_k = 0;
+  if (n == 0) return VR_OK;
+  hipStream_t st = as_stream(stream);
+  const KnLayout Y = kn_layout(ws, n, d, C, k);
+  if (n <= C + 1) {  // no cut: every row takes the exact scan (slots from n - 1 on: NaN, -1)
+    VR_TRY(exact_scan_k(X, n, d, ldx, nullptr, n, Y, k, r, nn, st));
+    g_last_fallback_k = n;
+    return VR_OK;
+  }
+  {
+    KtScope kt(KT_KNN_STAGE, 2.0 * (double)n * (double)d * sizeof(float), st);
+    const int64_t rows_per = (n + Y.chunks - 1) / Y.chunks;
+    k_knn_colsum<<<dim3((unsigned)((d + 255) / 256), (unsigned)Y.chunks), 256, 0, st>>>(X, n, d, ldx, rows_per,
+                                                                                      Y.colpart);
+    VR_CHECK_LAUNCH();
+    k_knn_colmean<float><<<(unsigned)((d + 255) / 256), 256, 0, st>>>(Y.colpart, n, d, Y.chunks, Y.mu);
+    VR_CHECK_LAUNCH();
+    k_knn_stage<<<(unsigned)Y.n_pad, 256, 0, st>>>(X, n, d, ldx, Y.mu, Y.Y, Y.d_pad, Y.a64, Y.a32);
+    VR_CHECK_LAUNCH();
+    k_knn_amax<<<1, 256, 0, st>>>(Y.a64, n, Y.amax, Y.fail_count);
+    VR_CHECK_LAUNCH();
+  }
+  VR_TRY(C == KN_C ? launch_cand<KN_L>(Y, n, st) : C == 12 ? launch_cand<13>(Y, n, st) : launch_cand<25>(Y, n, st));
+  const double u = 0x1p-24, du = (double)d * u;
+  const double efac = du < 0.5 ? 1.001 * (du / (1.0 - du) + 9.0 * u) : std::numeric_limits<double>::infinity();
+  {
+    KtScope kt(KT_KNN_RERANK, (double)n * C, st);
+    VR_TRY(C == KN_C ? launch_merge<KN_L>(Y, n, st) : C == 12 ? launch_merge<13>(Y, n, st)
+                                                              : launch_merge<25>(Y, n, st));
+    k_knn_rerank_k<<<(unsigned)((n + 3) / 4), 256, 0, st>>>(X, n, d, ldx, Y.cand, C, Y.cut, Y.a64, Y.amax, efac, k, r,
+                                                           nn, Y.fail_list, Y.fail_count);
+    VR_CHECK_LAUNCH();
+  }
+  int32_t failed = 0;
+  VR_CHECK_HIP(hipMemcpyAsync(&failed, Y.fail_count, sizeof(failed), hipMemcpyDeviceToHost, st));
+  VR_CHECK_HIP(hipStreamSynchronize(st));
+  if (failed < 0 || failed > n) {
+    set_error("vr_knn_f32: fallback count %d outside [0, %lld]", (int)failed, (long long)n);
+    return VR_EINTERNAL;
+  }
+  if (failed > 0) VR_TRY(exact_scan_k(X, n, d, ldx, Y.fail_list, failed, Y, k, r, nn, st));
+  g_last_fallback_k = failed;
+  return VR_OK;
+}
+
+int vr_mle_id_f64(const double* r, int64_t n, int k, double* out, void* stream) {
+  clear_error();
+  VR_REQUIRE(n >= 0 && k >= 2 && k <= KN_KMAX, "vr_mle_id_f64: bad n=%lld k=%d", (long long)n, k);
+  VR_REQUIRE(out != nullptr && (n == 0 || r != nullptr), "vr_mle_id_f64: null pointer");
+  k_mle_reduce<<<1, 256, 0, as_stream(stream)>>>(r, n, k, out);
+  VR_CHECK_LAUNCH();
+  return VR_OK;
+}
+
+int vr_mutual_knn_i32(const int32_t* nnA, const int32_t* nnB, int64_t n, int k, const int32_t* perms, int64_t P,
+                      int32_t* counts, int64_t* totals, void* stream) {
+  clear_error();
+  VR_REQUIRE(n >= 0 && n <= KN_NMAX && k >= 1 && k <= KN_KMAX && P >= 0 && P <= ((int64_t)1 << 18),
+             "vr_mutual_knn_i32: bad n=%lld k=%d P=%lld", (long long)n, k, (long long)P);
+  VR_REQUIRE(totals != nullptr && (n == 0 || (nnA != nullptr && nnB != nullptr)) && (P == 0 || perms != nullptr),
+             "vr_mutual_knn_i32: null pointer");
+  hipStream_t st = as_stream(stream);
+  VR_CHECK_HIP(hipMemsetAsync(totals, 0, (size_t)(1 + P) * sizeof(int64_t), st));
+  if (n == 0) return VR_OK;
+  const dim3 grid((unsigned)((n + 255) / 256), (unsigned)((1 + P + MK_SLOTS - 1) / MK_SLOTS));
+  k_mutual_knn<<<grid, 256, 0, st>>>(nnA, nnB, n, k, perms, 1 + P, counts,
+                                     reinterpret_cast<unsigned long long*>(totals));
   VR_CHECK_LAUNCH();
   return VR_OK;
 }
