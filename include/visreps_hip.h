@@ -254,7 +254,7 @@ int64_t vr_engine_est1_fallbacks(void);
 // Kernel-level HIP-event timing of the hot kernels, for pricing the dominant kernel against
 // its roofline on the stream it runs on (bench.py). Off by default; enabling clears the
 // totals. kernel: 0 k_rankB EST forms over bootstrap subsets, 1 k_rankB exact form, 2 k_rankA,
-// 3 k_join, 4 k_gram3p/k_gram3w (256^2 super-tiles), 5 k_gram3/k_gram (128^2 tiles),
+// 3 k_join, 4 k_gram3e (256^2 super-tiles), 5 k_gram3/k_gram (128^2 tiles),
 // 6 k_countA, 7 k_rankB EST 4 (the full-set pass: point estimates, phase-1 selections), 8 k_kwalk
 // (one Kendall stream walk of one pass), 9 k_cov (fp64 MFMA covariance / ridge Gram tiles),
 // 13 .. 16 the nearest-neighbour search of vr_knn2_f32: staging, k_knn_cand (units: FLOPs of the

@@ -15,7 +15,7 @@ if "Counter_Name" not in cols:
 meta = {}
 for r in csv.DictReader(open(sys.argv[1])):
     name = r["Kernel_Name"]
-    if "k_gram3e" not in name and "k_gram3p" not in name:
+    if "k_gram3e" not in name:
         continue
     d = int(r["Dispatch_Id"])
     rows[d][r["Counter_Name"]] = rows[d].get(r["Counter_Name"], 0.0) + float(r["Counter_Value"])

@@ -411,25 +411,23 @@ def test_rdm_generation_tail_split(dev, mode, monkeypatch):
     assert torch.equal(tail, tail.T) and torch.all(torch.diagonal(tail) == 0)
 
 
-@pytest.mark.parametrize("wide,kernel,d", [("1", "e", 1100), ("1", "p", 1100), ("0", "e", 1100),
-                                           ("1", "e", 40), ("1", "e", 9000), ("1", "p", 9000)])
-def test_rdm_wide_supertiles(dev, wide, kernel, d, monkeypatch):
+@pytest.mark.parametrize("wide,d", [("1", 1100), ("0", 1100), ("1", 40), ("1", 9000)])
+def test_rdm_wide_supertiles(dev, wide, d, monkeypatch):
     # n = 6000: 24 x 25 / 2 = 300 super-tiles of 256; super-tile rows [0, 15) run on the wide
-    # kernel (255 super-tiles = one generation; k_gram3e, or k_gram3p with
-    # VISREPS_GRAM_KERNEL=p), the 45 super-tiles below on the wide kernel split over k
-    # (k_gram_reduce_w) -- the 128-tile rows on k_gram3 when the wide kernel is off. Depths:
+    # kernel k_gram3e (255 super-tiles = one generation), the 45 super-tiles below on the
+    # wide kernel split over k (k_gram_reduce_w) -- the 128-tile rows on k_gram3 when the
+    # wide kernel is off. Depths:
     # 35 stages (odd, a ragged last stage), 2 stages, 282 stages (one accumulator flush).
     # Every scheme against fp64 -- within 5e-6, except at d = 40, where the hi/lo split's
-    # own precision over so few products reaches 1.2e-5 (both wide kernels alike,
-    # profiles/r3_gram_precision.log) and the RDM bound of DESIGN §4 (2e-5) applies; the
-    # product never takes the split kernel there (n^2 d < 1e10: the exact-fp32 kernel).
-    # Exact symmetry.
+    # own precision over so few products reaches 1.2e-5 (k_gram3e and its since-retired
+    # predecessor measured alike, profiles/r3_gram_precision.log) and the RDM bound of
+    # DESIGN §4 (2e-5) applies; the product never takes the split kernel there
+    # (n^2 d < 1e10: the exact-fp32 kernel). Exact symmetry.
     n = 6000
     feats = O.synthetic_features(n, [d], seed=13, relu=[True])[0]
     x = torch.from_numpy(feats).to(dev)
     monkeypatch.setenv("VISREPS_GRAM", "split")
     monkeypatch.setenv("VISREPS_GRAM_WIDE", wide)
-    monkeypatch.setenv("VISREPS_GRAM_KERNEL", kernel)
     got = R.compute_rdm(x).double()
     xd = x.double()
     xd = xd - xd.mean(1, keepdim=True)

@@ -154,7 +154,7 @@ enum KtKernel : int {
   KT_RANKB_EXACT = 1, // k_rankB, exact chunk-base form (VISREPS_ENGINE_EST=0, flagged reruns)
   KT_RANKA = 2,       // k_rankA (both forms)
   KT_JOIN = 3,        // k_join: a unit's A positions (and, for the exact form, A chunks)
-  KT_GRAM_WIDE = 4,   // k_gram3p / k_gram3w (256^2 super-tiles)
+  KT_GRAM_WIDE = 4,   // k_gram3e (256^2 super-tiles)
   KT_GRAM_TILE = 5,   // k_gram3 / k_gram (128^2 tiles)
   KT_COUNTA = 6,      // k_countA
   KT_RANKB_FULL = 7,  // k_rankB on the pass holding the full stimulus set (EST 4 A side: EST 3 B walks)

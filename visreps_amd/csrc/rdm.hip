@@ -786,368 +786,41 @@ __global__ __launch_bounds__(G_THREADS, 2) void k_gram3(GramParams P) {
 }
 
 // ------------------------------------------------------------------------------------
-// Wide split Gram: 256 x 256 super-tiles (2 x 2 of the 128-tiles), 8 waves as 2 x 4, each
-// wave 128 x 64 = 4 x 2 accumulators. Against k_gram3 it halves the global->LDS traffic
-// and the LDS writes per FLOP and cuts LDS fragment reads per MFMA from 2/3 to 1/2
-// (12 ds_read_b128 per 24 MFMAs per 16-k step). 147 KB of LDS: one block (8 waves) per CU.
-// Super-tile rows [0, R) of the upper triangle; a diagonal super-tile computes its lower
-// 128-tile too and writes only i <= j entries (mirrored), as the 128 kernel does.
+// Wide split Gram (k_gram3e): 256 x 256 super-tiles (2 x 2 of the 128-tiles), 8 waves as
+// 2 x 4, each wave a 128 x 64 block. Against k_gram3 it halves the global->LDS traffic and
+// the LDS writes per FLOP and cuts the LDS fragment reads per FLOP by a quarter. 128 KB of
+// LDS: one block (8 waves) per CU. It runs the super-tile rows [0, R) of the upper triangle
+// whole-depth and the rows [R, T2) split over k (gram_wide_rows, plan_range); a diagonal
+// super-tile computes its lower 128-tile too and writes only i <= j entries (mirrored), as
+// the 128 kernel does.
+// The kernel is phased, on v_mfma_f32_16x16x32_bf16: three products per k (hi.hi, hi.lo,
+// lo.hi), whole 32-k stage records in LDS (one 128-B record per row), moved global -> LDS
+// by global_load_lds (16 B per lane, no register staging), and the 16 x 16 MFMA shape,
+// which the chip clocks higher than 32 x 32 under load (MI355X_MICROARCH.md, DVFS
+// give-back item 7).
+// A stage is four 16-KB half-tiles (A rows 0-127 / 128-255, B the same), two stages
+// double-buffered (128 KB). A wave's 128 x 64 block is four quadrants (64-row half a0/a1
+// of its rows x 32-column half b0/b1): one phase per quadrant, 24 MFMAs each, in the
+// order (a0,b0) (a0,b1) (a1,b1) (a1,b0). Each phase first issues the LDS reads of the
+// fragments the NEXT phase needs (registers AX/AY for the A halves, BP/BQ for the B
+// halves: 96 VGPRs), then its MFMAs, which use fragments read one phase earlier:
+//   P0(t): MFMA a0 b0; read b1(t)        P1(t): MFMA a0 b1; read a1(t)
+//   P2(t): MFMA a1 b1; read a0(t+1)      P3(t): MFMA a1 b0; read b0(t+1)
+// One half-tile is staged per phase by LDS-DMA (two 1-KB pieces per wave):
+//   P0(t): A-bot(t+1)   P1(t): B-right(t+1)   P2(t): B-left(t+2)   P3(t): A-top(t+2)
+// so a buffer is restaged >= 2 phases after its last read (the reads of phase p are
+// consumed by phase p+1's MFMAs, which every wave has passed at phase p+2's barrier), and
+// each wave waits (counted vmcnt) before the barrier of the phase that first reads a
+// stage: P2(t) for the A halves of t+1 (B-right(t+1) may stay in flight), P3(t) for the B
+// halves (B-left(t+2) may). Diagonal super-tiles stage and read the A halves only.
+// Waves 4-7 run the same phases with their MFMAs half a phase late (e_stage_skew), so
+// the two waves of a SIMD do not sit in their issue/read heads at the same time.
+// LDS image of a half-tile: row r's 16-B chunk c at r * 128 + (c ^ ((r >> 1) & 7)) * 16;
+// a fragment read (16 rows of a 16-row block, one chunk per 16 lanes) then touches 16
+// distinct 16-B bank slots in each ds_read_b128 lane group.
 // ------------------------------------------------------------------------------------
 constexpr int WT = 256;               // super-tile edge
 constexpr int W_THREADS = 512;        // 8 waves
-constexpr int W_STAGE = WT * SROW;    // bf16 per panel per stage
-
-__device__ inline void load_rec_w(const GramParams& P, int64_t row0, int64_t st, u32x4 out[4]) {
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const int f = threadIdx.x + W_THREADS * s;
-    const int r = f >> 3, c = f & 7;
-    out[s] = *reinterpret_cast<const u32x4*>(P.planes + ((row0 + r) * P.nstage + st) * 64 + c * 8);
-  }
-}
-
-__device__ inline void store_rec_w(uint16_t* lds, const u32x4 v[4]) {
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const int f = threadIdx.x + W_THREADS * s;
-    const int r = f >> 3, c = f & 7;
-    *reinterpret_cast<u32x4*>(lds + r * SROW + c * 8) = v[s];
-  }
-}
-
-// Epilogue of one wave's 128 x 64 block (4 x 2 accumulators of 32 x 32).
-__device__ inline void gram_store_w(const GramParams& P, f32x16 (&acc)[4][2], int64_t row0,
-                                    int64_t col0, bool diag) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int wr = wid >> 2, wc = wid & 3, h = lane >> 5, l32 = lane & 31;
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int nn = 0; nn < 2; ++nn) {
-      const int64_t j = col0 + wc * 64 + nn * 32 + l32;
-      const float sj = (j < P.n) ? P.stdv[j] : 1.f;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int64_t ib = row0 + wr * 128 + m * 32 + 8 * g + 4 * h;
-        float v[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int64_t i = ib + e;
-          const float si = (i < P.n) ? P.stdv[i] : 1.f;
-          v[e] = rdm_value(acc[m][nn][4 * g + e], i, j, P, si, sj);
-        }
-        if (diag) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int64_t i = ib + e;
-            if (i <= j && j < P.n) {
-              P.rdm[i * P.ldr + j] = v[e];
-              if (i < j) P.rdm[j * P.ldr + i] = v[e];
-            }
-          }
-          continue;
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int64_t i = ib + e;
-          if (i < P.n && j < P.n) P.rdm[i * P.ldr + j] = v[e];
-        }
-        if (j < P.n) {
-          float* dst = P.rdm + j * P.ldr + ib;
-          if (P.vec && ib + 3 < P.n && ((P.ldr & 3) == 0)) {
-            f32x4 w = {v[0], v[1], v[2], v[3]};
-            *reinterpret_cast<f32x4*>(dst) = w;
-          } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              if (ib + e < P.n) dst[e] = v[e];
-          }
-        }
-      }
-    }
-}
-
-// Super-tile position p (row-major over super rows [0, R) of a T2 x T2 triangle).
-__device__ inline void super_tile(int p, int T2, int& bi, int& bj) { tile_coords(p, T2, bi, bj); }
-
-__global__ __launch_bounds__(W_THREADS, 1) void k_gram3w(GramParams P) {
-  __shared__ __attribute__((aligned(16))) uint16_t lds[2 * 2 * W_STAGE];  // [buf][A/B]
-  const int id = P.blk0 + (int)xcd_remap(blockIdx.x, (uint32_t)gridDim.x);
-  int bi, bj;
-  band_tile(id, P.tile0, P.tile_count, P.T, bi, bj);  // P.T = super-tiles per dimension here
-  const bool diag = (bi == bj);
-  const int64_t row0 = (int64_t)bi * WT, col0 = (int64_t)bj * WT;
-  const int ns = (int)P.nstage;
-
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int wr = wid >> 2, wc = wid & 3, h = lane >> 5, l32 = lane & 31;
-
-  f32x16 acc[4][2];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
-
-  u32x4 ga[4], gb[4];
-  load_rec_w(P, row0, 0, ga);
-  if (!diag) load_rec_w(P, col0, 0, gb);
-  store_rec_w(lds, ga);
-  if (!diag) store_rec_w(lds + W_STAGE, gb);
-  __syncthreads();
-  for (int kt = 0; kt < ns; ++kt) {
-    const int cur = kt & 1;
-    const uint16_t* As = lds + cur * 2 * W_STAGE;
-    const uint16_t* Bs = diag ? As : As + W_STAGE;
-    const bool more = kt + 1 < ns;
-    if (more) {
-      load_rec_w(P, row0, kt + 1, ga);
-      if (!diag) load_rec_w(P, col0, kt + 1, gb);
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      bf16x8 aH[4], aL[4], bH[2], bL[2];
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const uint16_t* ar = As + (wr * 128 + m * 32 + l32) * SROW + t * 16 + h * 8;
-        aH[m] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(ar));
-        aL[m] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(ar + 32));
-      }
-#pragma unroll
-      for (int nn = 0; nn < 2; ++nn) {
-        const uint16_t* br = Bs + (wc * 64 + nn * 32 + l32) * SROW + t * 16 + h * 8;
-        bH[nn] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(br));
-        bL[nn] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(br + 32));
-      }
-#pragma unroll
-      for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int nn = 0; nn < 2; ++nn)
-          acc[m][nn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aH[m], bH[nn], acc[m][nn], 0, 0, 0);
-#pragma unroll
-      for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int nn = 0; nn < 2; ++nn)
-          acc[m][nn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aH[m], bL[nn], acc[m][nn], 0, 0, 0);
-#pragma unroll
-      for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int nn = 0; nn < 2; ++nn)
-          acc[m][nn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aL[m], bH[nn], acc[m][nn], 0, 0, 0);
-    }
-    if (more) {
-      uint16_t* nxt = lds + (cur ^ 1) * 2 * W_STAGE;
-      store_rec_w(nxt, ga);
-      if (!diag) store_rec_w(nxt + W_STAGE, gb);
-    }
-    if (P.flush && more && (kt + 1) % P.flush == 0) {
-      gram_flush<WT>(acc, P.fbuf + (size_t)blockIdx.x * WT * WT, wr * 128, wc * 64, kt + 1 == P.flush);
-    }
-    __syncthreads();
-  }
-  if (P.flush && ns > P.flush) gram_unflush<WT>(acc, P.fbuf + (size_t)blockIdx.x * WT * WT, wr * 128, wc * 64);
-  gram_store_w(P, acc, row0, col0, diag);
-}
-
-// ------------------------------------------------------------------------------------
-// Pipelined wide split Gram (default for full RDMs): k_gram3w's 256 x 256 super-tiles and
-// 8-wave 2 x 4 decomposition, with the panels moved global -> LDS by global_load_lds
-// (16 B per lane, no register staging) in 16-k sub-stages: a sub-stage is, per row, the
-// 64 bytes [hi k0..15 | lo k0..15] of a 32-k record (two 32-B pieces), 16 KB per panel.
-// Four sub-stage slots (A + B = 32 KB each, 128 KB of LDS): while sub-stage q is consumed
-// (24 MFMAs per wave), q+1 and q+2 are in flight and q+3 is issued into the slot q-1 used.
-// Each wave waits only for its own loads of q (counted vmcnt: the loads of q+1 and q+2
-// stay in flight) and then a raw s_barrier, after which every wave's part of q has landed;
-// the slot rewritten by q+3 was last read in iteration q-1, before that barrier. The LDS
-// image is lane-linear per wave-instruction (16 rows x 64 B); 16-B chunk j of row r sits
-// at chunk j ^ ((r >> 2) & 3), applied on the global source address, so a fragment read
-// (32 rows, one chunk) touches 16 distinct 16-B bank slots per 16 lanes.
-// ------------------------------------------------------------------------------------
-constexpr int P_PANEL = WT * 64;       // bytes of one panel sub-stage
-constexpr int P_SLOT = 2 * P_PANEL;    // A + B
-constexpr int P_SLOTS = 4;            // sub-stage slots in LDS
-constexpr int P_AHEAD = P_SLOTS - 1;  // iteration q issues sub-stage q + P_AHEAD
-static_assert(P_AHEAD == 3, "the counted waits of gram3p_step / gram3p_loop assume 4 slots");
-
-// this wave's two 1-KB pieces (16 rows each) of a panel sub-stage: rows [16 (2 w + i), +16)
-__device__ inline void p_issue(const GramParams& P, char* panel, int64_t row0, int q) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int64_t st = q >> 1;
-  const int t = q & 1;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int rbase = (wid * 2 + i) * 16;
-    const int r = rbase + (lane >> 2);
-    const int j = (lane & 3) ^ ((r >> 2) & 3);  // the logical chunk this lane's slot holds
-    const int off = ((j & 2) << 5) + 32 * t + ((j & 1) << 4);
-    const char* src = reinterpret_cast<const char*>(P.planes) + ((row0 + r) * P.nstage + st) * 128 + off;
-    __builtin_amdgcn_global_load_lds(src, panel + rbase * 64, 16, 0, 0);
-  }
-}
-
-__device__ inline bf16x8 p_frag(const char* panel, int row, int j) {
-  return __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(panel + row * 64 + ((j ^ ((row >> 2) & 3)) << 4)));
-}
-
-template <int N>
-__device__ inline void p_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-struct PFrag {
-  bf16x8 aH[4], aL[4], bH[2], bL[2];
-};
-
-__device__ inline void p_read(const char* As, const char* Bs, PFrag& f) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int wr = wid >> 2, wc = wid & 3, h = lane >> 5, l32 = lane & 31;
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    const int r = wr * 128 + m * 32 + l32;
-    f.aH[m] = p_frag(As, r, h);
-    f.aL[m] = p_frag(As, r, 2 + h);
-  }
-#pragma unroll
-  for (int nn = 0; nn < 2; ++nn) {
-    const int r = wc * 64 + nn * 32 + l32;
-    f.bH[nn] = p_frag(Bs, r, h);
-    f.bL[nn] = p_frag(Bs, r, 2 + h);
-  }
-}
-
-__device__ inline void p_mfma(const PFrag& f, f32x16 (&acc)[4][2]) {
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int nn = 0; nn < 2; ++nn)
-      acc[m][nn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.aH[m], f.bH[nn], acc[m][nn], 0, 0, 0);
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int nn = 0; nn < 2; ++nn)
-      acc[m][nn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.aH[m], f.bL[nn], acc[m][nn], 0, 0, 0);
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int nn = 0; nn < 2; ++nn)
-      acc[m][nn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.aL[m], f.bH[nn], acc[m][nn], 0, 0, 0);
-}
-
-// Iteration q: sub-stage q's fragments are already in registers (cur); wait for this wave's
-// loads of q+1 (q+2 stays in flight), barrier, issue q+3 into the slot sub-stage q-1 used,
-// start the LDS reads of q+1 into nxt, then the 24 MFMAs of q, which do not wait for them.
-template <bool DIAG>
-__device__ inline void gram3p_step(const GramParams& P, char* lds, int64_t row0, int64_t col0, int q, int Q,
-                                   const PFrag& cur, PFrag& nxt, f32x16 (&acc)[4][2]) {
-  constexpr int PER = DIAG ? 2 : 4;  // glds per wave per sub-stage
-  if (q + 1 < Q) {
-    // this wave's loads of q+1 done; those of q+2 .. q+P_AHEAD-1 (issued) may stay in flight
-    const int left = Q - 2 - q;
-    if (left >= 1)
-      p_wait<PER>();
-    else
-      p_wait<0>();
-    __builtin_amdgcn_s_barrier();
-    if (q + P_AHEAD < Q) {
-      char* slot = lds + ((q + P_AHEAD) % P_SLOTS) * P_SLOT;
-      p_issue(P, slot, row0, q + P_AHEAD);
-      if (!DIAG) p_issue(P, slot + P_PANEL, col0, q + P_AHEAD);
-    }
-    const char* As = lds + ((q + 1) % P_SLOTS) * P_SLOT;
-    p_read(As, DIAG ? As : As + P_PANEL, nxt);
-  }
-  p_mfma(cur, acc);
-  // every P.flush stages (the same two-level sum as k_gram3w); its global loads and stores
-  // drain this wave's loads in flight (the compiler waits vmcnt(0)): correct, and rare
-  if (P.flush && (q & 1) && q + 1 < Q && ((q >> 1) + 1) % P.flush == 0) {
-    const int wid = threadIdx.x >> 6;
-    gram_flush<WT>(acc, P.fbuf + (size_t)blockIdx.x * WT * WT, (wid >> 2) * 128, (wid & 3) * 64,
-                   (q >> 1) + 1 == P.flush);
-  }
-}
-
-template <bool DIAG>
-__device__ inline void gram3p_loop(const GramParams& P, char* lds, int64_t row0, int64_t col0, int ns,
-                                   f32x16 (&acc)[4][2]) {
-  const int Q = 2 * ns;  // even
-  constexpr int PER = DIAG ? 2 : 4;
-  for (int q = 0; q < P_AHEAD && q < Q; ++q) {
-    char* slot = lds + q * P_SLOT;
-    p_issue(P, slot, row0, q);
-    if (!DIAG) p_issue(P, slot + P_PANEL, col0, q);
-  }
-  // sub-stage 0 landed: the loads of 1 .. P_AHEAD-1 may stay in flight
-  if (Q > 2)
-    p_wait<2 * PER>();
-  else if (Q > 1)
-    p_wait<PER>();
-  else
-    p_wait<0>();
-  __builtin_amdgcn_s_barrier();
-  PFrag f0, f1;
-  p_read(lds, DIAG ? lds : lds + P_PANEL, f0);
-  for (int q = 0; q < Q; q += 2) {  // two sub-stages per trip: the fragment sets swap roles
-    gram3p_step<DIAG>(P, lds, row0, col0, q, Q, f0, f1, acc);
-    gram3p_step<DIAG>(P, lds, row0, col0, q + 1, Q, f1, f0, acc);
-  }
-}
-
-// Split-K partial of one wave's 128 x 64 block: fp32 [split][super-tile][256 x 256]
-__device__ inline void gram_partial_w(const GramParams& P, f32x16 (&acc)[4][2], int split, int ltile) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int wr = wid >> 2, wc = wid & 3, h = lane >> 5, l32 = lane & 31;
-  float* out = P.partial + ((int64_t)split * P.tile_count + ltile) * (WT * WT);
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int nn = 0; nn < 2; ++nn) {
-      const int lj = wc * 64 + nn * 32 + l32;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int li = wr * 128 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        out[li * WT + lj] = acc[m][nn][r];
-      }
-    }
-}
-
-// Launch position id -> (super-tile, k split): split-major, so the blocks an XCD holds at
-// once are neighbouring tiles of one k range (shared panels in its L2). Split s covers
-// stages [s kslice / GK, min(nstage, (s + 1) kslice / GK)); one split: the whole depth.
-__global__ __launch_bounds__(W_THREADS, 1) void k_gram3p(GramParams P) {
-  __shared__ __attribute__((aligned(16))) char lds[P_SLOTS * P_SLOT];
-  const int id = P.blk0 + (int)xcd_remap(blockIdx.x, (uint32_t)gridDim.x);
-  const int split = id / P.tile_count, ltile = id % P.tile_count;
-  int bi, bj;
-  band_tile(ltile, P.tile0, P.tile_count, P.T, bi, bj);  // P.T = super-tiles per dimension here
-  const bool diag = (bi == bj);
-  const int64_t row0 = (int64_t)bi * WT, col0 = (int64_t)bj * WT;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int wr = wid >> 2, wc = wid & 3;
-  (void)lane;
-  const int64_t sper = P.kslice / GK;  // stages per split
-  const int64_t st0 = (int64_t)split * sper;
-  const int ns = (int)(P.nstage - st0 < sper ? P.nstage - st0 : sper);
-  GramParams S = P;
-  S.planes = P.planes + st0 * 64;  // records of stage st0 onwards (the row stride stays nstage)
-  f32x16 acc[4][2];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
-  if (diag)
-    gram3p_loop<true>(S, lds, row0, col0, ns, acc);
-  else
-    gram3p_loop<false>(S, lds, row0, col0, ns, acc);
-  if (P.flush && ns > P.flush)
-    gram_unflush<WT>(acc, P.fbuf + (size_t)blockIdx.x * WT * WT, wr * 128, wc * 64);
-  if (P.splits == 1)
-    gram_store_w(P, acc, row0, col0, diag);
-  else
-    gram_partial_w(P, acc, split, ltile);
-}
 
 // Sums the split partials of one super-tile in split order and applies the epilogue
 // (k_gram_reduce for 256-tiles): block (t, strip) handles rows [32 strip, +32) of
@@ -1185,35 +858,14 @@ __global__ __launch_bounds__(256) void k_gram_reduce_w(GramParams P) {
   }
 }
 
-// ------------------------------------------------------------------------------------
-// Phased wide split Gram on v_mfma_f32_16x16x32_bf16 (k_gram3e, VISREPS_GRAM_KERNEL=e).
-// The same 256 x 256 super-tiles, 8 waves as 2 x 4 and 128 x 64 wave tiles as k_gram3p,
-// the same three products per k, but whole 32-k stage records in LDS (one 128-B record
-// per row) and the 16 x 16 MFMA shape, which the chip clocks higher than 32 x 32 under
-// load (MI355X_MICROARCH.md, DVFS give-back item 7).
-// A stage is four 16-KB half-tiles (A rows 0-127 / 128-255, B the same), two stages
-// double-buffered (128 KB). A wave's 128 x 64 block is four quadrants (64-row half a0/a1
-// of its rows x 32-column half b0/b1): one phase per quadrant, 24 MFMAs each, in the
-// order (a0,b0) (a0,b1) (a1,b1) (a1,b0). Each phase first issues the LDS reads of the
-// fragments the NEXT phase needs (registers AX/AY for the A halves, BP/BQ for the B
-// halves: 96 VGPRs), then its MFMAs, which use fragments read one phase earlier:
-//   P0(t): MFMA a0 b0; read b1(t)        P1(t): MFMA a0 b1; read a1(t)
-//   P2(t): MFMA a1 b1; read a0(t+1)      P3(t): MFMA a1 b0; read b0(t+1)
-// One half-tile is staged per phase by LDS-DMA (two 1-KB pieces per wave):
-//   P0(t): A-bot(t+1)   P1(t): B-right(t+1)   P2(t): B-left(t+2)   P3(t): A-top(t+2)
-// so a buffer is restaged >= 2 phases after its last read (the reads of phase p are
-// consumed by phase p+1's MFMAs, which every wave has passed at phase p+2's barrier), and
-// each wave waits (counted vmcnt) before the barrier of the phase that first reads a
-// stage: P2(t) for the A halves of t+1 (B-right(t+1) may stay in flight), P3(t) for the B
-// halves (B-left(t+2) may). Diagonal super-tiles stage and read the A halves only.
-// Waves 4-7 run the same phases with their MFMAs half a phase late (e_stage_skew), so
-// the two waves of a SIMD do not sit in their issue/read heads at the same time.
-// LDS image of a half-tile: row r's 16-B chunk c at r * 128 + (c ^ ((r >> 1) & 7)) * 16;
-// a fragment read (16 rows of a 16-row block, one chunk per 16 lanes) then touches 16
-// distinct 16-B bank slots in each ds_read_b128 lane group.
-// ------------------------------------------------------------------------------------
 constexpr int E_HALF = 128 * 128;    // bytes of a half-tile stage (128 rows x 128 B)
 constexpr int E_STAGE = 4 * E_HALF;  // A-top, A-bot, B-left, B-right
+
+// counted wait: at most N of this wave's LDS-DMA loads still in flight
+template <int N>
+__device__ inline void p_wait() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
 
 // this wave's two 1-KB pieces (rows [16 wid, +16)) of half-tile h (0/1: A rows 0-127 /
 // 128-255 of the super-tile, 2/3: B) of stage st into the stage buffer sb. The lane part
@@ -1313,7 +965,7 @@ __device__ inline void e_mfma(const EFragA& a, const EFragB& b, f32x4 (&acc)[8][
 }
 
 // 16 x 16 C/D map: col = lane & 15, row = 4 (lane >> 4) + e. Flush buffer: the block's
-// 256 x 256 fp32 tile (k_gram3p's two-level sum, same interval).
+// 256 x 256 fp32 tile (the two-level sum of gram_flush, same interval).
 __device__ inline float* e_flush_base(float* buf) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   uint32_t off = (uint32_t)(((wid >> 2) * 128 + 4 * (lane >> 4)) * WT + (wid & 3) * 64 + (lane & 15));
@@ -1343,7 +995,7 @@ __device__ inline void e_unflush(f32x4 (&acc)[8][4], const float* buf) {
       for (int e = 0; e < 4; ++e) acc[i][j][e] += b[(i * 16 + e) * WT + j * 16];
 }
 
-// Epilogue of the wave's 128 x 64 block (8 x 4 tiles of 16 x 16), as gram_store_w: a
+// Epilogue of the wave's 128 x 64 block (8 x 4 tiles of 16 x 16), as gram_store: a
 // diagonal super-tile writes each i < j entry from its (i, j) accumulator to both places.
 template <bool ONE>
 __device__ inline void e_store(const GramParams& P, f32x4 (&acc)[8][4], int64_t row0, int64_t col0, bool diag) {
@@ -1628,8 +1280,10 @@ __device__ inline void e_tile(const GramParams& P, const GramParams& S, char* ld
     e_partial(P, acc, split, ltile);
 }
 
-// Launch position id -> (super-tile, k split) as k_gram3p: split-major; one split = the
-// whole depth (P.kslice = nstage * GK).
+// Launch position id -> (super-tile, k split): split-major, so the blocks an XCD holds at
+// once are neighbouring tiles of one k range (shared panels in its L2). Split s covers
+// stages [s kslice / GK, min(nstage, (s + 1) kslice / GK)); one split = the whole depth
+// (P.kslice = nstage * GK).
 template <bool ONE>
 __global__ __launch_bounds__(W_THREADS, 1) void k_gram3e(GramParams P) {
   __shared__ __attribute__((aligned(16))) char lds[2 * E_STAGE];
@@ -1652,22 +1306,9 @@ __global__ __launch_bounds__(W_THREADS, 1) void k_gram3e(GramParams P) {
     e_tile<ONE, false>(P, S, lds, row0, col0, ns, diag, split, ltile);
 }
 
-// The full-depth wide launches run k_gram3e (measured +3.5-8.5 % over k_gram3p on whole
-// RDMs at N = 10k, profiles/r3_gram_ab.log); VISREPS_GRAM_KERNEL=p selects k_gram3p (A/B).
 static bool env_flag(const char* name, bool dflt) {
   const char* e = getenv(name);
   return e && *e ? strcmp(e, "0") != 0 : dflt;
-}
-
-static bool gram_phased() {
-  const char* e = getenv("VISREPS_GRAM_KERNEL");
-  return !(e && strcmp(e, "p") == 0);
-}
-
-// VISREPS_GRAM_PIPE=0: the register-staged k_gram3w (A/B timing)
-static bool gram_pipe() {
-  const char* e = getenv("VISREPS_GRAM_PIPE");
-  return !(e && strcmp(e, "0") == 0);
 }
 
 // Sums the split partials of one tile in split order and applies the epilogue; the
@@ -1774,14 +1415,10 @@ static int64_t gram_tail(int64_t count) {
 }
 
 // Split-K partial floats of one tile range as run_split launches it (main + tail).
-static size_t range_partial(int64_t n, int64_t d, int64_t count, bool fit_one = false) {
+static size_t range_partial(int64_t n, int64_t d, int64_t count) {
   if (count <= 0) return 0;
   int T, ntiles, splits;
   int64_t kslice;
-  if (fit_one && count < 2 * num_cus()) {
-    gram_geometry(n, d, count, T, ntiles, splits, kslice, true);
-    return splits > 1 ? (size_t)splits * count * GT * GT : 0;
-  }
   const int64_t tail = gram_tail(count);
   gram_geometry(n, d, count - tail, T, ntiles, splits, kslice);
   size_t part = splits > 1 ? (size_t)splits * (count - tail) : 0;
@@ -1796,7 +1433,7 @@ static int64_t tri_start(int64_t r, int64_t T) { return r * T - r * (r - 1) / 2;
 
 // Super-tile rows [0, R) of the wide split kernel in a full-RDM launch (0: not used).
 // R is the largest whose super-tile count fits whole generations of one block per CU;
-// the 128-tile rows [2R, T) below them run on k_gram3 (generations + tail split).
+// the super-tile rows [R, T2) below them run on the wide kernel split over k (plan_range).
 // VISREPS_GRAM_WIDE=0 turns the wide kernel off (A/B timing).
 static int gram_wide_rows(int64_t n, int64_t d, bool split3) {
   if (!split3) return 0;
@@ -1813,18 +1450,18 @@ static int gram_wide_rows(int64_t n, int64_t d, bool split3) {
 
 // How a launch over 128-tiles [t0, t1) runs. Every tile of an RDM is computed the same way
 // whatever range it is launched in -- the full-RDM decomposition (super-tile rows [0, R) on
-// the wide kernel, whole depth per tile; the remainder rows [2R, T) as one run_split) --
+// the wide kernel, whole depth per tile; the remainder rows [R, T2) on the wide kernel
+// split over k, one generation, partials summed in split order by k_gram_reduce_w) --
 // so a range whose ends are super-tile row starts (tri_start(2r, T), r <= R) or the end of
 // the triangle gives tiles bit-identical to the full launch: the multi-GPU path splits an
-// RDM only at those boundaries (vr_rdm_range_aligned). Other ranges (legacy callers) run
-// as one run_split of their own (split-K geometry of the range: last-bit differences).
+// RDM only at those boundaries (vr_rdm_range_aligned). Other ranges (legacy callers), and
+// every range when there are no wide rows, run as one run_split over their 128-tiles
+// (split-K geometry of the range: last-bit differences).
 struct RangePlan {
-  bool wide = false;
+  bool wide = false;               // false: one run_split over [t0, t1)
   int64_t s0 = 0, s1 = 0;          // super-tiles [s0, s1) of the wide kernel, whole depth
-  int64_t r0 = 0, r_count = 0;     // super-tile rows [R, T2) (the triangle's end): wide, split-K
+  int64_t r0 = 0, r_count = 0;     // super-tiles [r0, r0 + r_count): rows [R, T2), split-K
   int r_splits = 1;
-  int64_t rem0 = 0, rem_count = 0;  // 128-tiles of the run_split part (unaligned ranges)
-  bool rem_fit = false;             // run_split's fit_one
 };
 
 // k splits of the wide kernel's remainder launch: enough blocks for one per CU, at least
@@ -1842,8 +1479,6 @@ static RangePlan plan_range(int64_t n, int64_t d, int64_t t0, int64_t t1, bool s
   RangePlan rp;
   const int64_t total = gram_tiles(n), T = (n + GT - 1) / GT, T2 = (n + WT - 1) / WT;
   const int R = gram_wide_rows(n, d, split3);
-  rp.rem0 = t0;
-  rp.rem_count = t1 - t0;
   if (R == 0 || t1 <= t0) return rp;
   int64_t r0 = -1, r1 = -1;
   for (int64_t r = 0; r <= R; ++r) {
@@ -1851,22 +1486,14 @@ static RangePlan plan_range(int64_t n, int64_t d, int64_t t0, int64_t t1, bool s
     if (tri_start(2 * r, T) == t1) r1 = r;
   }
   if (r0 < 0 || (t1 != total && r1 < 0)) return rp;  // not aligned: legacy run_split
-  const int64_t trem = tri_start(2 * (int64_t)R, T);
   rp.wide = true;
   rp.s0 = tri_start(r0, T2);
   rp.s1 = t1 == total ? tri_start(R, T2) : tri_start(r1, T2);
-  rp.rem_count = 0;
-  // The rows below R run on the wide kernel split over k (one generation, partials summed
-  // in split order by k_gram_reduce_w); VISREPS_GRAM_WIDE_REM=0 runs them as 128-tiles
-  // (run_split). With k_gram3e: +1.4 % on whole RDMs at D = 290,400, equal at 43,264
-  // (profiles/r3_gram_ab.log) -- the wide kernel's per-CU rate, less +16 % work (the
+  // The rows below R run on the wide kernel split over k. Against running them as
+  // 128-tiles on k_gram3 that measured +1.4 % on whole RDMs at D = 290,400 and equal at
+  // 43,264 (profiles/r3_gram_ab.log) -- the wide kernel's per-CU rate, less +16 % work (the
   // diagonal super-tiles' lower quadrants), 220 of 256 CUs busy and the partial round trip.
-  static const bool wide_rem = !(getenv("VISREPS_GRAM_WIDE_REM") && strcmp(getenv("VISREPS_GRAM_WIDE_REM"), "0") == 0);
-  if (t1 == total && !wide_rem) {
-    rp.rem0 = trem;
-    rp.rem_count = total - trem;
-    rp.rem_fit = true;
-  } else if (t1 == total) {
+  if (t1 == total) {
     rp.r0 = tri_start(R, T2);
     rp.r_count = T2 * (T2 + 1) / 2 - rp.r0;
     rp.r_splits = wide_rem_splits(rp.r_count, (d + GK - 1) / GK);
@@ -1892,8 +1519,8 @@ static size_t gram_ws(int64_t n, int64_t d, int64_t t0, int64_t t1, bool split3,
                       float** stdv, float** partial, uint16_t** planes, float** fbuf = nullptr,
                       bool own_planes = true, uint32_t** flag = nullptr) {
   const RangePlan rp = plan_range(n, d, t0, t1, split3);
-  size_t part = range_partial(n, d, rp.rem_count, rp.rem_fit);
-  if (rp.r_splits > 1) part = std::max(part, (size_t)rp.r_count * rp.r_splits * WT * WT);
+  const size_t part = rp.wide ? (rp.r_splits > 1 ? (size_t)rp.r_count * rp.r_splits * WT * WT : 0)
+                              : range_partial(n, d, t1 - t0);
   Carver c(base);
   float* m = c.take<float>((size_t)n);
   float* s = c.take<float>((size_t)n);
@@ -1911,6 +1538,15 @@ static size_t gram_ws(int64_t n, int64_t d, int64_t t0, int64_t t1, bool split3,
   if (partial) *partial = p;
   if (planes) *planes = pl;
   return c.bytes();
+}
+
+// 128-tile `tile` of the row-major upper triangle of n rows -> (block row, block col)
+static void host_tile_coords(int64_t n, int64_t tile, int& bi, int& bj) {
+  const int T = (int)((n + GT - 1) / GT);
+  int p = (int)tile, r = 0;
+  while (r + 1 < T && (int64_t)(r + 1) * T - (int64_t)(r + 1) * r / 2 <= p) ++r;
+  bi = r;
+  bj = r + (p - (r * T - r * (r - 1) / 2));
 }
 
 }  // namespace vr
@@ -1945,11 +1581,8 @@ int vr_rdm_range_aligned(int64_t n, int64_t d, int64_t tile_begin, int64_t tile_
 
 int64_t vr_rdm_tile_cost(int64_t n, int64_t tile) {
   // elements of the tile on or above the diagonal (the work the balancer spreads)
-  int T = (int)((n + GT - 1) / GT), bi, bj;
-  int p = (int)tile, r = 0;
-  while (r + 1 < T && (int64_t)(r + 1) * T - (int64_t)(r + 1) * r / 2 <= p) ++r;
-  bi = r;
-  bj = r + (p - (r * T - r * (r - 1) / 2));
+  int bi, bj;
+  host_tile_coords(n, tile, bi, bj);
   const int64_t h = std::min<int64_t>(GT, n - (int64_t)bi * GT), w = std::min<int64_t>(GT, n - (int64_t)bj * GT);
   return bi == bj ? h * (h + 1) / 2 : h * w;
 }
@@ -1959,10 +1592,8 @@ int vr_rdm_tile_rect(int64_t n, int64_t tile, int64_t* row0, int64_t* col0, int6
   VR_REQUIRE(n > 0 && tile >= 0 && tile < gram_tiles(n), "vr_rdm_tile_rect: tile %lld of %lld",
              (long long)tile, (long long)(n > 0 ? gram_tiles(n) : 0));
   VR_REQUIRE(row0 && col0 && rows && cols, "vr_rdm_tile_rect: null output");
-  const int T = (int)((n + GT - 1) / GT);
-  int p = (int)tile, r = 0;
-  while (r + 1 < T && (int64_t)(r + 1) * T - (int64_t)(r + 1) * r / 2 <= p) ++r;
-  const int bi = r, bj = r + (p - (r * T - r * (r - 1) / 2));
+  int bi, bj;
+  host_tile_coords(n, tile, bi, bj);
   *row0 = (int64_t)bi * GT;
   *col0 = (int64_t)bj * GT;
   *rows = std::min<int64_t>(GT, n - *row0);
@@ -2025,7 +1656,7 @@ static int rdm_launch(const void* Xv, int64_t n, int64_t d, int64_t ldx, float* 
   P.raw = raw ? 1 : 0;
   P.dk = d;
   bool one = false;  // bf16 input, one product per k (the default for bf16; VISREPS_GRAM_ONE=0: split)
-  if (bf16 && !pre.planes && !raw && gram_phased() && env_flag("VISREPS_GRAM_ONE", true)) {
+  if (bf16 && !pre.planes && !raw && env_flag("VISREPS_GRAM_ONE", true)) {
     const int64_t rows = (n + WT - 1) / WT * WT, nst1 = (d + 2 * GK - 1) / (2 * GK);
     VR_CHECK_HIP(hipMemsetAsync(one_flag, 0, sizeof(uint32_t), st));
     k_stats_one<<<(unsigned)rows, RSTAT_BS, 0, st>>>(static_cast<const uint16_t*>(Xv), n, d, ldx, nst1, correction,
@@ -2103,65 +1734,51 @@ static int rdm_launch(const void* Xv, int64_t n, int64_t d, int64_t ldx, float* 
     }
     return VR_OK;
   };
-  // fit_one: a range smaller than one generation splits over k into at most one
-  // generation (floor) instead of spilling a few blocks into a second one (ceil)
-  auto run_split = [&](int64_t t0, int64_t count, bool fit_one) -> int {
-    if (fit_one && count < 2 * num_cus()) return run_range(t0, count, true);
+  // a multi-generation range's small tail runs as its own split-K launch (gram_tail)
+  auto run_split = [&](int64_t t0, int64_t count) -> int {
     const int64_t tail = gram_tail(count);
     VR_TRY(run_range(t0, count - tail, false));
     return run_range(t0 + count - tail, tail, true);
   };
   const RangePlan rp = plan_range(n, d, tile_begin, tile_end, split3);
-  if (!rp.wide) return run_split(tile_begin, tile_end - tile_begin, false);
-  // wide super-tiles [s0, s1) (rows of the full RDM's wide part), then the 128-tile rows
-  // below them when the range holds them
+  if (!rp.wide) return run_split(tile_begin, tile_end - tile_begin);
+  // `nblk` blocks of the wide kernel (super-tiles x k splits of W), one per CU at a time
+  const int gen = num_cus();
+  auto run_wide = [&](GramParams& W, int nblk) -> int {
+    for (int b0 = 0; b0 < nblk; b0 += gen) {
+      W.blk0 = b0;
+      const int nb = std::min(gen, nblk - b0);
+      KtScope kt(KT_GRAM_WIDE, 2.0 * (double)nb / W.splits * WT * WT * (double)d, st);
+      if (W.one)
+        k_gram3e<true><<<(unsigned)nb, W_THREADS, 0, st>>>(W);
+      else
+        k_gram3e<false><<<(unsigned)nb, W_THREADS, 0, st>>>(W);
+      VR_CHECK_LAUNCH();
+    }
+    return VR_OK;
+  };
+  // wide super-tiles [s0, s1) (rows of the full RDM's wide part), whole depth
   GramParams W = P;
   W.T = (int)((n + WT - 1) / WT);
   W.tile0 = (int)rp.s0;
   W.tile_count = (int)(rp.s1 - rp.s0);
   W.splits = 1;
   W.kslice = P.nstage * GK;
-  const int gen = num_cus();
-  const bool pipe = gram_pipe(), phased = gram_phased();
   W.flush = (size_t)gen * WT * WT <= gram_fbuf_floats() ? flush_stages : 0;
-  for (int b0 = 0; b0 < W.tile_count; b0 += gen) {
-    W.blk0 = b0;
-    KtScope kt(KT_GRAM_WIDE, 2.0 * (double)std::min(gen, W.tile_count - b0) * WT * WT * (double)d, st);
-    if (phased && W.one)
-      k_gram3e<true><<<(unsigned)std::min(gen, W.tile_count - b0), W_THREADS, 0, st>>>(W);
-    else if (phased)
-      k_gram3e<false><<<(unsigned)std::min(gen, W.tile_count - b0), W_THREADS, 0, st>>>(W);
-    else if (pipe)
-      k_gram3p<<<(unsigned)std::min(gen, W.tile_count - b0), W_THREADS, 0, st>>>(W);
-    else
-      k_gram3w<<<(unsigned)std::min(gen, W.tile_count - b0), W_THREADS, 0, st>>>(W);
-    VR_CHECK_LAUNCH();
-  }
+  VR_TRY(run_wide(W, W.tile_count));
   if (rp.r_count > 0) {  // rows [R, T2): split over k, partials summed in split order
     GramParams Rm = W;
     Rm.tile0 = (int)rp.r0;
     Rm.tile_count = (int)rp.r_count;
     Rm.splits = rp.r_splits;
     Rm.kslice = (P.nstage + rp.r_splits - 1) / rp.r_splits * GK;
-    const int nblk = Rm.tile_count * Rm.splits;
-    for (int b0 = 0; b0 < nblk; b0 += gen) {
-      Rm.blk0 = b0;
-      const int nb = std::min(gen, nblk - b0);
-      KtScope kt(KT_GRAM_WIDE, 2.0 * (double)nb / Rm.splits * WT * WT * (double)d, st);
-      if (phased && Rm.one)
-        k_gram3e<true><<<(unsigned)nb, W_THREADS, 0, st>>>(Rm);
-      else if (phased)
-        k_gram3e<false><<<(unsigned)nb, W_THREADS, 0, st>>>(Rm);
-      else
-        k_gram3p<<<(unsigned)nb, W_THREADS, 0, st>>>(Rm);
-      VR_CHECK_LAUNCH();
-    }
+    VR_TRY(run_wide(Rm, Rm.tile_count * Rm.splits));
     if (Rm.splits > 1) {
       k_gram_reduce_w<<<dim3((unsigned)Rm.tile_count, WT / 32), 256, 0, st>>>(Rm);
       VR_CHECK_LAUNCH();
     }
   }
-  return run_split(rp.rem0, rp.rem_count, true);
+  return VR_OK;
 }
 
 int vr_rdm_pearson_f32(const float* X, int64_t n, int64_t d, int64_t ldx, float* rdm,
