@@ -77,13 +77,37 @@ static int est_bits(int64_t M, uint32_t maxrows = EST_NC, uint32_t target = 96) 
 }
 static uint32_t est_intervals(int64_t M, int b) { return (uint32_t)((M + ((int64_t)1 << b) - 1) >> b); }
 
-// EST form by default (VISREPS_ENGINE_EST=0: every pass exact). Measured on the bench RDMs
-// (profiles/r2_engine_est3.log): k_rankB 1.56 ms per pass in EST 3 against 1.96 ms in the
-// exact form. The table form (EST 1) and the masks-from-L2 variants measured 1.86-2.04 ms
-// (profiles/r2_engine_ab.log): their per-pair table reads cost what the base gather saved.
-static bool engine_est() {
-  const char* e = getenv("VISREPS_ENGINE_EST");
-  return !(e && strcmp(e, "0") == 0);
+// Run-time switches. engine_env reads them once per call (never cached: tests change them
+// between the calls of one process) and EngineCfg carries the snapshot, so engine_cfg, the
+// workspace queries and the runners of one call all see the same values.
+//   VISREPS_ENGINE_  default  meaning
+//   EST              on       "0": every pass in the exact chunk-base form. On the bench RDMs k_rankB takes 1.56 ms
+//                             per pass in EST 3 against 1.96 ms in the exact form (profiles/r2_engine_est3.log)
+//   EST_MODE         3        1: EST passes use the per-lane interval table (EST 1). It and the masks-from-L2 variants
+//                             measured 1.86-2.04 ms (profiles/r2_engine_ab.log): their per-pair table reads cost what
+//                             the base gather saved
+//   EST_PREDICT      1        0: skip the up-front check of the EST 3 estimate; a failing estimate is then caught by
+//                             the first pass's flags, at the cost of that pass
+//   EST1_FALLBACK    1        0: a call failing the up-front check runs in the exact form, never in EST 1
+//   MASKS            (unset)  "global": the exact kernels and k_countA read the masks from L2 (A/B timing)
+//   GRID             1        0: a grid call runs its regions one by one
+//   GRID_LDS         1        0: the fused grid walk reads the masks from L2 at any n (A/B, tests)
+struct EngineEnv {
+  bool est, est_predict, est1_fallback, masks_global, grid, grid_lds;
+  int est_mode;  // 1 or 3
+};
+static EngineEnv engine_env() {
+  auto str_is = [](const char* name, const char* v) { const char* e = getenv(name); return e && strcmp(e, v) == 0; };
+  auto num = [](const char* name, int dflt) { const char* e = getenv(name); return e && *e ? atoi(e) : dflt; };
+  EngineEnv v;
+  v.est = !str_is("VISREPS_ENGINE_EST", "0");
+  v.est_mode = num("VISREPS_ENGINE_EST_MODE", 3) == 1 ? 1 : 3;
+  v.est_predict = num("VISREPS_ENGINE_EST_PREDICT", 1) != 0;
+  v.est1_fallback = num("VISREPS_ENGINE_EST1_FALLBACK", 1) != 0;
+  v.masks_global = str_is("VISREPS_ENGINE_MASKS", "global");
+  v.grid = num("VISREPS_ENGINE_GRID", 1) != 0;
+  v.grid_lds = num("VISREPS_ENGINE_GRID_LDS", 1) != 0;
+  return v;
 }
 
 // Launch shape. The walks are bound by the latency of their random TB gathers, so they run
@@ -106,12 +130,8 @@ struct EngineCfg {
   uint32_t est_ratioA;
   bool prejoined = false;  // the units' A positions arrive joined (vr_bootstrap_spearman_multi_joined)
   size_t tab;         // EST rank walks' dynamic LDS: [masks] + table
+  EngineEnv env;      // the call's switches
 };
-
-static int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e && *e ? atoi(e) : dflt;
-}
 
 constexpr int SEGS_PER_WAVE = 4;  // most EST A-side segments per resident wave (workspace bound)
 // EST B walks take segments of >= 256 positions from a work queue, one per resident wave;
@@ -122,15 +142,15 @@ static uint32_t est_segments(int64_t M, int est_nwaves) {
   return (uint32_t)std::max<int64_t>(1, std::min<int64_t>(by_len, (int64_t)est_nwaves));
 }
 
-// mode: the EST estimate (0: VISREPS_ENGINE_EST_MODE, default 3; 1: the per-lane table, the
-// fallback of a call whose EST 3 estimate fails its up-front check)
-static EngineCfg engine_cfg(int64_t n, int mode = 0) {
+// mode: the EST estimate (0: env.est_mode; 1: the per-lane table, the fallback of a call
+// whose EST 3 estimate fails its up-front check)
+static EngineCfg engine_cfg(int64_t n, const EngineEnv& env = engine_env(), int mode = 0) {
   EngineCfg c;
+  c.env = env;
   const int64_t M = pairs_of(n);
   const size_t need = (size_t)n * sizeof(uint64_t);
   const size_t cap = 160 * 1024 - 1024;
-  const char* e = getenv("VISREPS_ENGINE_MASKS");  // "global": masks from L2 (A/B timing)
-  c.use_lds = need <= cap && !(e && strcmp(e, "global") == 0);
+  c.use_lds = need <= cap && !env.masks_global;
   c.lds = c.use_lds ? need : 0;
   const int per_cu = std::max<int>(1, std::min<int>(2048 / ENG_THREADS, (int)(cap / std::max<size_t>(c.lds, 1))));
   c.grid = num_cus() * per_cu;
@@ -140,7 +160,7 @@ static EngineCfg engine_cfg(int64_t n, int mode = 0) {
   // >= 1 row beside the masks; otherwise masks from L2 and the table alone in LDS.
   const size_t row = (size_t)LANES * sizeof(uint2);
   const size_t per_wg = cap / per_cu;
-  c.est_mode = mode > 0 ? mode : (env_int("VISREPS_ENGINE_EST_MODE", 3) == 1 ? 1 : 3);
+  c.est_mode = mode > 0 ? mode : env.est_mode;
   c.est_lds = c.use_lds && per_wg >= need + (c.est_mode == 3 ? 0 : row);
   uint32_t rows_fit =
       c.est_lds ? (uint32_t)std::min<size_t>(EST_NC, (per_wg - need) / row) : (uint32_t)EST_NC;
@@ -1731,119 +1751,174 @@ static int allow_big_lds(K kernel) {
   return VR_OK;
 }
 
+// One engine call as every runner sees it, built once per entry point.
+struct EngineCall {
+  int64_t n, M;
+  const int32_t* idx;
+  int64_t k, n_sets;
+  int full_first;
+  int64_t total;  // subsets scored: the n_sets of idx, after the full set if full_first
+  int lw;         // subsets per pass (the lanes in use): LANES, or 1 for the triangle entry point
+  uint2 e3;       // the EST 3 / 4 window (est3_params)
+  EngineCfg cfg;  // launch shape and switches (cfg.env)
+  hipStream_t st;
+  int64_t npass() const { return (total + lw - 1) / lw; }
+  int nl(int64_t p) const { return (int)std::min<int64_t>(lw, total - p * lw); }  // subsets of pass p
+  bool full0(int64_t p) const { return full_first && p == 0; }                     // pass p holds the full set
+};
+static EngineCall engine_call(int64_t n, const int32_t* idx, int64_t k, int64_t n_sets, int full_first, int lw,
+                              const EngineCfg& cfg, void* stream) {
+  const int64_t M = pairs_of(n);
+  // (a point-only call holds the full set alone: its window is the full set's, so lane 0's
+  // EST 4 shift is at most 1 -- with k's window instead a group of > 3 tied pairs could
+  // shift below 1 and flag the pass)
+  const uint2 e3 = est3_params(n_sets > 0 ? k : n, M);
+  return {n, M, idx, k, n_sets, full_first, n_sets + (full_first ? 1 : 0), lw, e3, cfg, as_stream(stream)};
+}
+
 // A side of a pass (shared by every B plan of the call), exact form: TB rows in A order,
 // chunk bases baseA, A segment tie sums and the included-pair totals totA.
 template <bool LDS, bool FULL, typename TBT, bool BTA>
-static int pass_a(const PlanView& A, int64_t n, const EngineWs& E, int lw, const EngineCfg& cfg,
-                  hipStream_t st) {
+static int pass_a(const EngineCall& c, const PlanView& A, const EngineWs& E) {
   VR_ONCE(VR_TRY(allow_big_lds(k_rankA<LDS, FULL, TBT, BTA, false>)));
-  const int64_t M = pairs_of(n);
-  const uint32_t nch = plan_nchunks(M);
-  const uint32_t nseg = (uint32_t)cfg.nwaves;
+  const uint32_t nch = plan_nchunks(c.M);
+  const uint32_t nseg = (uint32_t)c.cfg.nwaves;
   {
-    KtScope kt(KT_RANKA, (double)M, st);
-    k_rankA<LDS, FULL, TBT, BTA, false><<<cfg.grid, ENG_THREADS, cfg.lds, st>>>(
-        A.codes, A.gstart, A.chunk_g, A.gflag, nch, E.masks, n, static_cast<TBT*>(E.TB), lw, E.lpA,
+    KtScope kt(KT_RANKA, (double)c.M, c.st);
+    k_rankA<LDS, FULL, TBT, BTA, false><<<c.cfg.grid, ENG_THREADS, c.cfg.lds, c.st>>>(
+        A.codes, A.gstart, A.chunk_g, A.gflag, nch, E.masks, c.n, static_cast<TBT*>(E.TB), c.lw, E.lpA,
         E.segA_tot, E.segA_part, nseg, EstA{}, nullptr, nullptr);
     VR_CHECK_LAUNCH();
   }
-  VR_TRY(lane_scan(E.segA_tot, nseg, E.bsum, E.segA_pre, E.totA, st));
-  const size_t nb = ((size_t)nch * LANES + 255) / 256;
-  k_add_base<<<(unsigned)nb, 256, 0, st>>>(E.lpA, E.segA_pre, nch, nseg, E.baseA);
+  VR_TRY(lane_scan(E.segA_tot, nseg, E.bsum, E.segA_pre, E.totA, c.st));
+  k_add_base<<<(unsigned)(((size_t)nch * LANES + 255) / 256), 256, 0, c.st>>>(E.lpA, E.segA_pre, nch, nseg, E.baseA);
   VR_CHECK_LAUNCH();
   return VR_OK;
+}
+
+// Test hook (vr_test_engine_inject(p), a test-only export; -1 = off, the default): after
+// the A walk of EST pass p, add 1 to the TB entries of lanes 1..63 of one pair row -- a
+// B-side recovery error the A walk's checks cannot see. The tail's invariants must flag
+// the pass and the exact re-run must restore every score (tests/test_engine_est.py). No
+// environment variable is read: the product path cannot be switched into it by accident.
+static std::atomic<int64_t> g_test_inject{-1};
+
+__global__ void k_inject_tb(uint16_t* __restrict__ TB, uint32_t row, int stride, int lanes) {
+  const int lane = threadIdx.x;
+  if (lane >= 1 && lane < lanes) TB[(size_t)row * stride + lane] += 1u;
 }
 
 // A side of a pass, EST form: count pre-pass -> segment bases and the interval table ->
 // absolute u16 ranks in A order (flagging *viol when one is not recoverable). The count
 // pre-pass reads the masks from LDS when they fit (CL), the rank walk from L2.
+// EM: EST 1, or EST 3 with EST 4 for the pass holding the full set (EST 3 needs every lane to hold k stimuli).
+// The pass's work-queue counters are cleared first: the A walk's and nb_own B slots -- the B walks of a region run
+// on its own take this workspace's queue, a fused region passes 0 (the grid walks take region 0's).
+// inject_lanes > 0: the test hook, on that many lanes.
 template <int EM, bool CL, bool FULL, bool BTA>
-static int pass_a_est(const PlanView& A, int64_t n, const EngineWs& E, int lw, int nl, const EngineCfg& cfg,
-                      uint2 e3, uint32_t* viol, hipStream_t st) {
+static int pass_a_est(const EngineCall& c, const PlanView& A, const EngineWs& E, int nl, int64_t nb_own,
+                      uint32_t* viol, int inject_lanes) {
   VR_ONCE(VR_TRY(allow_big_lds(k_countA<CL, FULL>)); VR_TRY(allow_big_lds(k_rankA<CL, FULL, uint16_t, BTA, EM>)));
-  const int64_t M = pairs_of(n);
-  const uint32_t nch = plan_nchunks(M);
+  const EngineCfg& cfg = c.cfg;
+  VR_CHECK_HIP(hipMemsetAsync(E.queue, 0, sizeof(uint32_t) * (size_t)std::min<int64_t>(QS_RANKB + nb_own, QSLOTS),
+                              c.st));
+  const uint32_t nch = plan_nchunks(c.M);
   const uint32_t nseg = cfg.est_nsegA;
   const int bits = cfg.est_b;
   const uint32_t nc = cfg.est_rows;
   {
-    KtScope kt(KT_COUNTA, (double)M, st);
-    k_countA<CL, FULL><<<cfg.est_grid, ENG_THREADS, CL ? (size_t)n * sizeof(uint64_t) : 0, st>>>(
-        A.codes, A.gstart, A.chunk_g, nch, E.masks, n, lw, bits, E.c0rel, E.c0seg, E.segA_tot, nseg, E.segposA);
+    KtScope kt(KT_COUNTA, (double)c.M, c.st);
+    k_countA<CL, FULL><<<cfg.est_grid, ENG_THREADS, CL ? (size_t)c.n * sizeof(uint64_t) : 0, c.st>>>(
+        A.codes, A.gstart, A.chunk_g, nch, E.masks, c.n, c.lw, bits, E.c0rel, E.c0seg, E.segA_tot, nseg, E.segposA);
     VR_CHECK_LAUNCH();
   }
-  VR_TRY(lane_scan(E.segA_tot, nseg, E.bsum, E.segA_pre, E.totA, st));
+  VR_TRY(lane_scan(E.segA_tot, nseg, E.bsum, E.segA_pre, E.totA, c.st));
   if constexpr (EM >= 3)
-    k_c0_u<<<1, 1, 0, st>>>(e3.x, e3.y, E.ftab);
+    k_c0_u<<<1, 1, 0, c.st>>>(c.e3.x, c.e3.y, E.ftab);
   else
-    k_c0<<<nc, LANES, 0, st>>>(E.c0rel, E.c0seg, E.segA_pre, E.totA, nc, bits, M, E.ftab);
+    k_c0<<<nc, LANES, 0, c.st>>>(E.c0rel, E.c0seg, E.segA_pre, E.totA, nc, bits, c.M, E.ftab);
   VR_CHECK_LAUNCH();
   const EstA est{E.segA_pre, E.ftab, nc, bits, viol, nl};
   {
-    KtScope kt(KT_RANKA, (double)M, st);
-    k_rankA<CL, FULL, uint16_t, BTA, EM><<<cfg.est_grid, ENG_THREADS, cfg.tab, st>>>(
-        A.codes, A.gstart, A.chunk_g, A.gflag, nch, E.masks, n, static_cast<uint16_t*>(E.TB), lw, E.lpA,
+    KtScope kt(KT_RANKA, (double)c.M, c.st);
+    k_rankA<CL, FULL, uint16_t, BTA, EM><<<cfg.est_grid, ENG_THREADS, cfg.tab, c.st>>>(
+        A.codes, A.gstart, A.chunk_g, A.gflag, nch, E.masks, c.n, static_cast<uint16_t*>(E.TB), c.lw, E.lpA,
         E.segA_tot, E.segA_part, nseg, est, E.segposA, E.queue + QS_RANKA);
+    VR_CHECK_LAUNCH();
+  }
+  if (inject_lanes > 0) {
+    k_inject_tb<<<1, LANES, 0, c.st>>>(static_cast<uint16_t*>(E.TB), (uint32_t)(c.M / 2), c.lw, inject_lanes);
     VR_CHECK_LAUNCH();
   }
   return VR_OK;
 }
 
-// EST 3 up-front check of a call's first pass (masks already built): the count pre-pass at
+// The EST 3 estimate is checked against the first pass's A counts before any join or pass.
+// (Only when some lane holds a bootstrap subset: the full-set lane is exact by construction,
+// and a point-only call -- phase 1's 56 -- would pay a host sync for nothing.)
+static bool est_check_on(const EngineCall& c) {
+  return c.cfg.env.est && c.cfg.est_mode == 3 && c.n_sets > 0 && c.cfg.env.est_predict;
+}
+// That check for one A plan (the first pass's masks already built): the count pre-pass at
 // boundaries every 2^b positions (<= EST_NC of them), its scan, k_est_predict. bad <- the
 // wave-uniform estimate cannot hold these A ranks (strongly structured RDMs: per-stimulus
 // effects move a subset's count hundreds of thousands of pairs off the line), so the call
-// goes to the exact form before spending an EST pass and its joins on a flag.
+// goes to the exact form before spending an EST pass and its joins on a flag. counted: the
+// caller acts on it (a fused region that fails only leaves for a run on its own, which
+// checks and counts again).
 template <bool CL, bool FULL>
-static int est_predict(const PlanView& A, int64_t n, const EngineWs& E, int lw, int nl, bool full0,
-                       const EngineCfg& cfg, uint2 e3, hipStream_t st, bool& bad) {
+static int est_check(const EngineCall& c, const PlanView& A, const EngineWs& E, bool counted, bool& bad) {
   VR_ONCE(VR_TRY(allow_big_lds(k_countA<CL, FULL>)));
-  const int64_t M = pairs_of(n);
-  const uint32_t nch = plan_nchunks(M);
-  const uint32_t nseg = cfg.est_nsegA;
+  const uint32_t nch = plan_nchunks(c.M);
+  const uint32_t nseg = c.cfg.est_nsegA;
   int b = 12;
-  while (((M + ((int64_t)1 << b) - 1) >> b) > (int64_t)EST_NC) ++b;
-  const uint32_t nc = est_intervals(M, b);
+  while (((c.M + ((int64_t)1 << b) - 1) >> b) > (int64_t)EST_NC) ++b;
+  const uint32_t nc = est_intervals(c.M, b);
   {
-    KtScope kt(KT_COUNTA, (double)M, st);
-    k_countA<CL, FULL><<<cfg.est_grid, ENG_THREADS, CL ? (size_t)n * sizeof(uint64_t) : 0, st>>>(
-        A.codes, A.gstart, A.chunk_g, nch, E.masks, n, lw, b, E.c0rel, E.c0seg, E.segA_tot, nseg, E.segposA);
+    KtScope kt(KT_COUNTA, (double)c.M, c.st);
+    k_countA<CL, FULL><<<c.cfg.est_grid, ENG_THREADS, CL ? (size_t)c.n * sizeof(uint64_t) : 0, c.st>>>(
+        A.codes, A.gstart, A.chunk_g, nch, E.masks, c.n, c.lw, b, E.c0rel, E.c0seg, E.segA_tot, nseg, E.segposA);
     VR_CHECK_LAUNCH();
   }
-  VR_TRY(lane_scan(E.segA_tot, nseg, E.bsum, E.segA_pre, E.totA, st));
+  VR_TRY(lane_scan(E.segA_tot, nseg, E.bsum, E.segA_pre, E.totA, c.st));
   uint32_t* flag = E.viol;  // pass flags are cleared before the EST passes
-  VR_CHECK_HIP(hipMemsetAsync(flag, 0, sizeof(uint32_t), st));
-  k_est_predict<<<nc, LANES, 0, st>>>(E.c0rel, E.c0seg, E.segA_pre, b, e3.y, nl, full0 ? 1 : 0, flag);
+  VR_CHECK_HIP(hipMemsetAsync(flag, 0, sizeof(uint32_t), c.st));
+  k_est_predict<<<nc, LANES, 0, c.st>>>(E.c0rel, E.c0seg, E.segA_pre, b, c.e3.y, c.nl(0), c.full_first ? 1 : 0, flag);
   VR_CHECK_LAUNCH();
   uint32_t h = 0;
-  VR_CHECK_HIP(hipMemcpyAsync(&h, flag, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  VR_CHECK_HIP(hipStreamSynchronize(st));
+  VR_CHECK_HIP(hipMemcpyAsync(&h, flag, sizeof(uint32_t), hipMemcpyDeviceToHost, c.st));
+  VR_CHECK_HIP(hipStreamSynchronize(c.st));
   bad = h != 0;
+  if (bad && counted) g_est_predicted.fetch_add(1);
+  return VR_OK;
+}
+
+// B plan u's EST segment starts and the work-queue counter of its walk in E (slots past QSLOTS
+// are reused, each cleared right before its launch; the others are cleared once per pass)
+static int est_slot_b(const EngineWs& E, int64_t u, hipStream_t st, const uint32_t*& segpos, uint32_t*& q) {
+  segpos = E.segposB + E.segstride * (size_t)u;
+  q = E.queue + QS_RANKB + (size_t)u % (size_t)(QSLOTS - QS_RANKB);
+  if (u >= QSLOTS - QS_RANKB) VR_CHECK_HIP(hipMemsetAsync(q, 0, sizeof(uint32_t), st));
   return VR_OK;
 }
 
 // B walk of a pass for one B plan (unit slot u of the segment partials), joined to A by
 // posA_byB (and, in the exact form, chunkA_byB: the A chunks; EST walks get none)
 template <bool LDS, bool FULL, typename TBT, bool BTB, int EST>
-static int walk_b(const PlanView& B, const uint32_t* posA_byB, const uint32_t* chunkA_byB, int64_t n,
-                  const EngineWs& E, int lw, int64_t u, const EngineCfg& cfg, hipStream_t st, int kt_slot = -1) {
+static int walk_b(const EngineCall& c, const PlanView& B, const uint32_t* posA_byB, const uint32_t* chunkA_byB,
+                  const EngineWs& E, int64_t u, int kt_slot = -1) {
   VR_ONCE(VR_TRY(allow_big_lds(k_rankB<LDS, FULL, TBT, BTB, EST>)));
-  const int64_t M = pairs_of(n);
-  const uint32_t nch = plan_nchunks(M);
+  const EngineCfg& cfg = c.cfg;
+  const uint32_t nch = plan_nchunks(c.M);
   const uint32_t nseg = EST ? cfg.est_nseg : (uint32_t)cfg.nwaves;
   const size_t us = (size_t)E.useg * (size_t)u;
-  // EST: unit u's B segment starts and its queue counter (slots past QSLOTS are reused, each
-  // cleared right before its launch)
-  const uint32_t* segpos = EST ? E.segposB + E.segstride * (size_t)u : nullptr;
+  const uint32_t* segpos = nullptr;
   uint32_t* q = nullptr;
-  if constexpr (EST != 0) {
-    q = E.queue + QS_RANKB + (size_t)u % (size_t)(QSLOTS - QS_RANKB);
-    if (u >= QSLOTS - QS_RANKB) VR_CHECK_HIP(hipMemsetAsync(q, 0, sizeof(uint32_t), st));
-  }
+  if constexpr (EST != 0) VR_TRY(est_slot_b(E, u, c.st, segpos, q));
   {
-    KtScope kt(kt_slot >= 0 ? kt_slot : EST ? KT_RANKB_EST : KT_RANKB_EXACT, (double)M, st);
-    k_rankB<LDS, FULL, TBT, BTB, EST><<<EST ? cfg.est_grid : cfg.grid, ENG_THREADS, EST ? cfg.tab : cfg.lds, st>>>(
-        B.codes, B.gstart, B.chunk_g, B.gflag, nch, E.masks, n, static_cast<const TBT*>(E.TB), lw,
+    KtScope kt(kt_slot >= 0 ? kt_slot : EST ? KT_RANKB_EST : KT_RANKB_EXACT, (double)c.M, c.st);
+    k_rankB<LDS, FULL, TBT, BTB, EST><<<EST ? cfg.est_grid : cfg.grid, ENG_THREADS, EST ? cfg.tab : cfg.lds, c.st>>>(
+        B.codes, B.gstart, B.chunk_g, B.gflag, nch, E.masks, c.n, static_cast<const TBT*>(E.TB), c.lw,
         posA_byB, chunkA_byB, E.baseA, E.segB_tot + us, E.segB_part + us * PB_N, nseg, E.ftab,
         EST ? cfg.est_rows : 0, EST ? cfg.est_b : 0, segpos, q);
     VR_CHECK_LAUNCH();
@@ -1852,17 +1927,17 @@ static int walk_b(const PlanView& B, const uint32_t* posA_byB, const uint32_t* c
 }
 
 // Tail of a pass for units [0, nb) (their B walks done): the nl scores of each, unit j's at
-// scores + j * score_ld. nan_b[j]: unit j's B plan holds a NaN. *viol <- 1 when a unit's
+// scores + j * score_ld. hb[j]: unit j's B plan header (has_nan). *viol <- 1 when a unit's
 // sums break the invariants (k_tail_top).
 static int tail_units(const EngineWs& E, int64_t nb, uint32_t nseg, uint32_t ratioA, bool a_nan,
-                      const std::vector<char>& nan_b, int nl, double* scores, int64_t score_ld, uint32_t* viol,
+                      const std::vector<PlanHeader>& hb, int nl, double* scores, int64_t score_ld, uint32_t* viol,
                       hipStream_t st, const uint64_t* corr = nullptr) {
   const uint32_t nsb = scan_blocks(nseg);
   for (int64_t u0 = 0; u0 < nb; u0 += 64) {  // 64 units per launch (the NaN bitmask)
     const int64_t cnt = std::min<int64_t>(64, nb - u0);
     uint64_t nan_units = 0;
     for (int64_t j = 0; j < cnt; ++j)
-      if (nan_b[(size_t)(u0 + j)]) nan_units |= 1ull << j;
+      if (hb[(size_t)(u0 + j)].has_nan) nan_units |= 1ull << j;
     const size_t us = (size_t)E.useg * (size_t)u0;
     k_tail_part<<<dim3(nsb, (unsigned)cnt), 1024, 0, st>>>(E.segA_part, E.segB_part + us * PB_N,
                                                             E.segB_tot + us, nseg, E.useg, E.fpart, ratioA);
@@ -1891,249 +1966,267 @@ static int with_pass_tag(bool lds, bool full, bool narrow, Fn&& fn) {
   return narrow ? fn(PassTag<false, false, uint16_t>{}) : fn(PassTag<false, false, uint32_t>{});
 }
 
-// One A plan against nb B plans (one unit each). Per pass of 64 subsets the A side runs
+// ---- steps shared by the per-region runner (run_solo) and the region-fused one (run_engine_grid)
+
+// Plan headers of a call's A and B plans, fetched together (one host sync)
+struct Headers {
+  std::vector<PlanHeader> a, b;
+  bool b_small = true;  // B tie groups < 2^16 (the fused walks' 64-bit tie sums)
+};
+static int fetch_headers(const PlanView* As, int R, const PlanView* Bs, int64_t nb, hipStream_t st, Headers& H) {
+  H.a.resize((size_t)R);
+  H.b.resize((size_t)nb);
+  for (int r = 0; r < R; ++r)
+    VR_CHECK_HIP(hipMemcpyAsync(&H.a[(size_t)r], As[r].hdr, sizeof(PlanHeader), hipMemcpyDeviceToHost, st));
+  for (int64_t j = 0; j < nb; ++j)
+    VR_CHECK_HIP(hipMemcpyAsync(&H.b[(size_t)j], Bs[j].hdr, sizeof(PlanHeader), hipMemcpyDeviceToHost, st));
+  VR_CHECK_HIP(hipStreamSynchronize(st));
+  for (const PlanHeader& h : H.b) H.b_small = H.b_small && h.max_group < 65536u;
+  return VR_OK;
+}
+
+// EST segment starts (k_seg_table), once per call: of one A plan, into its workspace ...
+static int seg_table(const EngineCall& c, const PlanView& P, uint32_t nseg, uint32_t* segpos) {
+  k_seg_table<<<(nseg + 256) / 256, 256, 0, c.st>>>(P.gstart, P.hdr, c.M, nseg, segpos);
+  VR_CHECK_LAUNCH();
+  return VR_OK;
+}
+static int seg_table_a(const EngineCall& c, const PlanView& A, const EngineWs& E) {
+  return seg_table(c, A, c.cfg.est_nsegA, E.segposA);
+}
+// ... and of every B plan (they depend on the B plan only: a grid call keeps region 0's)
+static int seg_tables_b(const EngineCall& c, const PlanView* Bs, int64_t nb, const EngineWs& E) {
+  for (int64_t j = 0; j < nb; ++j) VR_TRY(seg_table(c, Bs[j], c.cfg.est_nseg, E.segposB + E.segstride * (size_t)j));
+  return VR_OK;
+}
+
+// EST 4 (the pass holding the full set): lane 0's ranks are stored shifted (est4_shift), so
+// its B walks are the EST 3 kernel (timed on their own slot) and k_full_corr supplies lane
+// 0's shift sums, here for the nb units of one region (joins[2 j]: unit j's A positions)
+static int full_corr_units(const EngineCall& c, const PlanView* Bs, const std::vector<PlanHeader>& hb, int64_t nb,
+                           uint32_t* const* joins, const EngineWs& E) {
+  for (int64_t j = 0; j < nb; ++j) {
+    KtScope kt(KT_FULL_CORR, (double)c.M, c.st);
+    k_full_corr<<<CORR_BLK, 256, 0, c.st>>>(joins[2 * j], Bs[j].gflag, Bs[j].gstart, hb[(size_t)j].G, c.M, c.e3.y,
+                                            E.corr + (size_t)j * CORR_N);
+    VR_CHECK_LAUNCH();
+  }
+  return VR_OK;
+}
+
+// Flags of one region's EST passes [p0, p0 + cnt) (E.viol[0, cnt), one host sync): the
+// flagged passes are appended to `flagged`. counted: the caller re-runs them in the exact
+// form, so each counts as a re-run (a fused region whose first pass is flagged only leaves
+// for a solo run, which flags and counts it again).
+static int harvest_flags(const EngineCall& c, const EngineWs& E, int64_t p0, int64_t cnt, bool counted,
+                         std::vector<int64_t>& flagged) {
+  std::vector<uint32_t> flags((size_t)cnt);
+  VR_CHECK_HIP(hipMemcpyAsync(flags.data(), E.viol, flags.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c.st));
+  VR_CHECK_HIP(hipStreamSynchronize(c.st));
+  for (int64_t i = 0; i < cnt; ++i) {
+    if (!flags[(size_t)i]) continue;
+    flagged.push_back(p0 + i);
+    if (!counted) continue;
+    g_est_reruns.fetch_add(1);
+    // only the tail invariants flagged it: the A walk's window checks passed, so the B side
+    // recovered a wrong rank (an A-flagged pass breaks the invariants too, as expected)
+    if ((flags[(size_t)i] & 3u) == 2u) g_est_tail_flags.fetch_add(1);
+  }
+  return VR_OK;
+}
+
+// ---- one A plan against nb B plans (one unit each). Per pass of 64 subsets the A side runs
 // once and every B side reads its TB rows, so a plan shared by several units (a neural
 // RDM against every model layer, evals.py:323-373 loops regions x layers) pays its rank
 // walk once per pass. Spearman is symmetric in its two arguments and every sum is exact,
 // so scores equal the per-unit calls bit for bit.
 // Scores of B j: scores[j * score_ld + s] for the `total` subsets (full set first if
-// full_first), 64 per pass. joins: nb pairs of M-element (posA_byB, chunkA_byB) arrays.
+// full_first), lw per pass. joins: nb pairs of M-element (posA_byB, chunkA_byB) arrays.
 // Passes run in the EST form; the few it flags (and every pass, with VISREPS_ENGINE_EST=0)
 // run in the exact chunk-base form, which needs the chunkA joins too.
-// Test hook (vr_test_engine_inject(p), a test-only export; -1 = off, the default): after
-// the A walk of EST pass p, add 1 to the TB entries of lanes 1..63 of one pair row -- a
-// B-side recovery error the A walk's checks cannot see. The tail's invariants must flag
-// the pass and the exact re-run must restore every score (tests/test_engine_est.py). No
-// environment variable is read: the product path cannot be switched into it by accident.
-static std::atomic<int64_t> g_test_inject{-1};
-
-__global__ void k_inject_tb(uint16_t* __restrict__ TB, uint32_t row, int stride, int lanes) {
-  const int lane = threadIdx.x;
-  if (lane >= 1 && lane < lanes) TB[(size_t)row * stride + lane] += 1u;
-}
-
-// exact_passes (non-null): run only these passes, in the exact form (a grid call's flagged
-// passes of one region; the rest of its scores stand)
-static int run_engine_multi_impl(const PlanView& A, const PlanView* Bs, int64_t nb, int64_t n,
-                                 const int32_t* idx, int64_t k, int64_t n_sets, int full_first,
-                                 double* scores, int64_t score_ld, uint32_t* const* joins,
-                                 const EngineWs& E, int lw, const EngineCfg& cfg, hipStream_t st,
-                                 const std::vector<int64_t>* exact_passes = nullptr) {
-  const int64_t M = pairs_of(n);
-  uint32_t* const xbad = E.viol + EST_MAX_PASSES;  // exact-form passes' invariant flag
-  const int64_t inject = g_test_inject.load(std::memory_order_relaxed);
-  const int64_t total = n_sets + (full_first ? 1 : 0);
-  if (total == 0 || nb == 0) return VR_OK;
-  if (M == 0) {  // no pairs: every score is NaN (scipy on empty input)
-    for (int64_t j = 0; j < nb; ++j) {
-      k_fill_nan<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(scores + j * score_ld, total);
-      VR_CHECK_LAUNCH();
-    }
-    return VR_OK;
-  }
+struct Solo {
+  const PlanView& A;
+  const PlanView* Bs;
+  int64_t nb;
+  double* scores;
+  int64_t score_ld;
+  uint32_t* const* joins;
+  const EngineWs& E;
+  Headers H;               // solo_begin
+  int second = JOIN_NONE;  // what the joins' second arrays hold
   // u16 chunk-relative ranks y~ <= 2 span + 1 need every chunk span (< L + largest tie
   // group of A) <= 32767; 64-bit tie sums need every group below 2^16
-  std::vector<PlanHeader> h((size_t)nb + 1);
-  VR_CHECK_HIP(hipMemcpyAsync(&h[0], A.hdr, sizeof(PlanHeader), hipMemcpyDeviceToHost, st));
-  for (int64_t j = 0; j < nb; ++j)
-    VR_CHECK_HIP(hipMemcpyAsync(&h[(size_t)j + 1], Bs[j].hdr, sizeof(PlanHeader),
-                                hipMemcpyDeviceToHost, st));
-  VR_CHECK_HIP(hipStreamSynchronize(st));
-  const bool narrow = (uint64_t)PLAN_L + h[0].max_group <= 32767u;
-  std::vector<char> nan_b((size_t)nb);
-  for (int64_t j = 0; j < nb; ++j) nan_b[(size_t)j] = h[(size_t)j + 1].has_nan != 0;
-  const bool bigA = h[0].max_group >= 65536u;
-  const bool est = engine_est();
-  // (a point-only call holds the full set alone: its window is the full set's, so lane 0's
-  // EST 4 shift is at most 1 -- with k's window instead a group of > 3 tied pairs could
-  // shift below 1 and flag the pass)
-  const uint2 e3 = est3_params(n_sets > 0 ? k : n, M);
-  int second = JOIN_NONE;  // what the joins' second arrays hold
-  auto join = [&](int mode) -> int {
-    for (int64_t j = 0; j < nb; ++j) {
-      KtScope kt(KT_JOIN, (double)M, st);
-      k_join<<<(unsigned)((M + 255) / 256), 256, 0, st>>>(Bs[j].codes, M, n, A.gstart, A.chunk_g,
-                                                         plan_chunk_len(M), plan_nchunks(M), A.pos_map,
-                                                         joins[2 * j], joins[2 * j + 1], mode);
-      VR_CHECK_LAUNCH();
-    }
-    second = mode;
-    return VR_OK;
-  };
-  // EST segment starts of the A plan and of every B plan (k_seg_table), once per call
-  if (est) {
-    const uint32_t ns = cfg.est_nseg, nsA = cfg.est_nsegA;
-    k_seg_table<<<(nsA + 256) / 256, 256, 0, st>>>(A.gstart, A.hdr, M, nsA, E.segposA);
-    VR_CHECK_LAUNCH();
-    for (int64_t j = 0; j < nb; ++j) {
-      k_seg_table<<<(ns + 256) / 256, 256, 0, st>>>(Bs[j].gstart, Bs[j].hdr, M, ns,
-                                                    E.segposB + E.segstride * (size_t)j);
-      VR_CHECK_LAUNCH();
-    }
-  }
-  // the EST 3 estimate checked against the first pass's A counts before any join or pass
-  // (VISREPS_ENGINE_EST_PREDICT=0: skip the check; a failing estimate is then caught by the
-  // first pass's flags, at the cost of that pass)
-  bool predicted_bad = false;
-  // (only when some lane holds a bootstrap subset: the full-set lane is exact by
-  // construction, and a point-only call -- phase 1's 56 -- would pay a host sync for nothing)
-  if (est && cfg.est_mode == 3 && n_sets > 0 && !exact_passes && env_int("VISREPS_ENGINE_EST_PREDICT", 1) != 0) {
-    const int nl0 = (int)std::min<int64_t>(lw, total);
-    VR_TRY(build_pass_masks(idx, k, 0, nl0, full_first, E.masks, n, st));
-    VR_TRY(with_pass_tag(cfg.est_lds, lw == LANES, true, [&](auto tag) -> int {
-      using Tg = decltype(tag);
-      return est_predict<Tg::lds, Tg::full>(A, n, E, lw, nl0, full_first != 0, cfg, e3, st, predicted_bad);
-    }));
-  }
-  // (pre-joined units already hold their A positions: an EST call reading only those skips
-  // the join; an exact-form one rewrites them with the same values beside the A chunks)
-  if (!predicted_bad && !exact_passes && !(cfg.prejoined && est)) VR_TRY(join(est ? JOIN_NONE : JOIN_CHUNK));
-  // the exact chunk-base form of subsets [set0, set0 + nl), nl <= lw
-  auto exact_pass = [&](auto tag, int64_t set0, int nl) -> int {
+  bool narrow() const { return (uint64_t)PLAN_L + H.a[0].max_group <= 32767u; }
+  bool bigA() const { return H.a[0].max_group >= 65536u; }
+  bool bigB(int64_t j) const { return H.b[(size_t)j].max_group >= 65536u; }
+};
+
+// What every run on one region starts with: its headers and, for EST, its segment tables
+static int solo_begin(const EngineCall& c, Solo& S) {
+  VR_TRY(fetch_headers(&S.A, 1, S.Bs, S.nb, c.st, S.H));
+  if (!c.cfg.env.est) return VR_OK;
+  VR_TRY(seg_table_a(c, S.A, S.E));
+  return seg_tables_b(c, S.Bs, S.nb, S.E);
+}
+
+// The up-front estimate check of a region run on its own
+static int solo_check(const EngineCall& c, Solo& S, bool& bad) {
+  if (!est_check_on(c)) return VR_OK;
+  VR_TRY(build_pass_masks(c.idx, c.k, 0, c.nl(0), c.full_first, S.E.masks, c.n, c.st));
+  return with_pass_tag(c.cfg.est_lds, c.lw == LANES, true, [&](auto tag) -> int {
     using Tg = decltype(tag);
-    using TBT = typename Tg::tbt;
-    VR_TRY(build_pass_masks(idx, k, set0, nl, full_first, E.masks, n, st));
-    VR_TRY((bigA ? pass_a<Tg::lds, Tg::full, TBT, true>(A, n, E, lw, cfg, st)
-                 : pass_a<Tg::lds, Tg::full, TBT, false>(A, n, E, lw, cfg, st)));
-    for (int64_t j = 0; j < nb; ++j) {
-      const uint32_t* pj = joins[2 * j];
-      const uint32_t* cj = joins[2 * j + 1];
-      VR_TRY((h[(size_t)j + 1].max_group >= 65536u
-                  ? walk_b<Tg::lds, Tg::full, TBT, true, 0>(Bs[j], pj, cj, n, E, lw, j, cfg, st)
-                  : walk_b<Tg::lds, Tg::full, TBT, false, 0>(Bs[j], pj, cj, n, E, lw, j, cfg, st)));
-    }
-    return tail_units(E, nb, (uint32_t)cfg.nwaves, 1u, h[0].has_nan != 0, nan_b, nl, scores + set0, score_ld, xbad,
-                      st);
-  };
-  // subsets [s0, total) in exact passes of lw
-  auto exact_from = [&](int64_t s0) -> int {
-    if (second != JOIN_CHUNK) VR_TRY(join(JOIN_CHUNK));
-    return with_pass_tag(cfg.use_lds, lw == LANES, narrow, [&](auto tag) -> int {
-      for (int64_t set0 = s0; set0 < total; set0 += lw)
-        VR_TRY(exact_pass(tag, set0, (int)std::min<int64_t>(lw, total - set0)));
-      return VR_OK;
-    });
-  };
-  if (exact_passes) {
-    VR_TRY(join(JOIN_CHUNK));
-    return with_pass_tag(cfg.use_lds, lw == LANES, narrow, [&](auto tag) -> int {
-      for (int64_t p : *exact_passes) {
-        const int64_t set0 = p * lw;
-        if (set0 < total) VR_TRY(exact_pass(tag, set0, (int)std::min<int64_t>(lw, total - set0)));
-      }
-      return VR_OK;
-    });
+    return est_check<Tg::lds, Tg::full>(c, S.A, S.E, true, bad);
+  });
+}
+
+static int join_units(const EngineCall& c, Solo& S, int mode) {
+  for (int64_t j = 0; j < S.nb; ++j) {
+    KtScope kt(KT_JOIN, (double)c.M, c.st);
+    k_join<<<(unsigned)((c.M + 255) / 256), 256, 0, c.st>>>(S.Bs[j].codes, c.M, c.n, S.A.gstart, S.A.chunk_g,
+                                                           plan_chunk_len(c.M), plan_nchunks(c.M), S.A.pos_map,
+                                                           S.joins[2 * j], S.joins[2 * j + 1], mode);
+    VR_CHECK_LAUNCH();
   }
-  if (!est) return exact_from(0);
-  if (predicted_bad) {
-    g_est_predicted.fetch_add(1);
-    // The lane-uniform EST 3 window cannot hold these counts (per-stimulus structure moves a
-    // subset's included count further from the line than 2^14 pairs: it grows ~ n^1.5, so
-    // large triangles cross it first). EST 1 follows each lane's own counts (an interpolated
-    // table whose knots are the lane's counts at <= 144 boundaries, one LDS read per pair),
-    // one gather per pair like EST 3; its flagged passes are re-run exact as ever. The exact
-    // form from the start only with VISREPS_ENGINE_EST1_FALLBACK=0 or a point-only call.
-    // (Only where the exact form reads its masks from L2 too, n > 20,352: below that the exact
-    // walks keep the masks in LDS and EST 1, whose table takes that LDS, measured slower --
-    // 79 vs 73 ms per unit on bench.structured_est_probe's RDM at N = 10k; at 20,500 EST 1
-    // won, 215 vs 234 ms, profiles/r6_large_n_probe_v2.log.)
-    if (lw == LANES && !cfg.use_lds && env_int("VISREPS_ENGINE_EST1_FALLBACK", 1) != 0) {
-      EngineCfg c1 = engine_cfg(n, 1);
-      c1.prejoined = cfg.prejoined;
-      if (c1.nwaves == cfg.nwaves && c1.est_nsegA <= (uint32_t)cfg.nwaves * SEGS_PER_WAVE) {
-        g_est1_fallbacks.fetch_add(1);
-        return run_engine_multi_impl(A, Bs, nb, n, idx, k, n_sets, full_first, scores, score_ld, joins, E, lw, c1,
-                                     st);
-      }
-    }
-    return exact_from(0);
-  }
-  const int64_t npass = (total + lw - 1) / lw;  // lw subsets per EST pass
-  const int64_t pfirst = 0;
+  S.second = mode;
+  return VR_OK;
+}
+
+// Pass p in the exact chunk-base form
+template <class Tg>
+static int exact_pass(const EngineCall& c, Solo& S, Tg, int64_t p) {
+  using TBT = typename Tg::tbt;
+  const EngineWs& E = S.E;
+  const int nl = c.nl(p);
+  VR_TRY(build_pass_masks(c.idx, c.k, p * c.lw, nl, c.full_first, E.masks, c.n, c.st));
+  VR_TRY((S.bigA() ? pass_a<Tg::lds, Tg::full, TBT, true>(c, S.A, E) : pass_a<Tg::lds, Tg::full, TBT, false>(c, S.A, E)));
+  for (int64_t j = 0; j < S.nb; ++j)
+    VR_TRY((S.bigB(j) ? walk_b<Tg::lds, Tg::full, TBT, true, 0>(c, S.Bs[j], S.joins[2 * j], S.joins[2 * j + 1], E, j)
+                      : walk_b<Tg::lds, Tg::full, TBT, false, 0>(c, S.Bs[j], S.joins[2 * j], S.joins[2 * j + 1], E, j)));
+  uint32_t* const xbad = E.viol + EST_MAX_PASSES;  // exact-form passes' invariant flag (run_engine_multi)
+  return tail_units(E, S.nb, (uint32_t)c.cfg.nwaves, 1u, S.H.a[0].has_nan != 0, S.H.b, nl,
+                    S.scores + p * c.lw, S.score_ld, xbad, c.st);
+}
+
+// Only these passes, in the exact form: an EST call's flagged passes (of a region run on its
+// own, or of a fused region of a grid call: the rest of its scores stand)
+static int exact_passes(const EngineCall& c, Solo& S, const std::vector<int64_t>& passes) {
+  if (passes.empty()) return VR_OK;
+  if (S.second != JOIN_CHUNK) VR_TRY(join_units(c, S, JOIN_CHUNK));
+  return with_pass_tag(c.cfg.use_lds, c.lw == LANES, S.narrow(), [&](auto tag) -> int {
+    for (int64_t p : passes)
+      if (p < c.npass()) VR_TRY(exact_pass(c, S, tag, p));
+    return VR_OK;
+  });
+}
+// Passes [p0, npass) in the exact form
+static int exact_from(const EngineCall& c, Solo& S, int64_t p0) {
+  std::vector<int64_t> passes;
+  for (int64_t p = p0; p < c.npass(); ++p) passes.push_back(p);
+  return exact_passes(c, S, passes);
+}
+
+// EST pass p of a region run on its own, in form EM (its masks built): A side -> walk_b per
+// unit (EST walks read the A positions alone; EST 4 walks in the EST 3 kernel) -> correction
+// and tail
+template <int EM, bool LDS, bool FULL>
+static int est_pass(const EngineCall& c, Solo& S, int64_t p, uint32_t* viol, int inject_lanes) {
+  const EngineWs& E = S.E;
+  const int nl = c.nl(p);
+  VR_TRY((S.bigA() ? pass_a_est<EM, LDS, FULL, true>(c, S.A, E, nl, S.nb, viol, inject_lanes)
+                   : pass_a_est<EM, LDS, FULL, false>(c, S.A, E, nl, S.nb, viol, inject_lanes)));
+  constexpr int EB = EM == 4 ? 3 : EM;
+  const int kts = EM == 4 ? KT_RANKB_FULL : -1;
+  for (int64_t j = 0; j < S.nb; ++j)
+    VR_TRY((S.bigB(j) ? walk_b<LDS, FULL, uint16_t, true, EB>(c, S.Bs[j], S.joins[2 * j], nullptr, E, j, kts)
+                      : walk_b<LDS, FULL, uint16_t, false, EB>(c, S.Bs[j], S.joins[2 * j], nullptr, E, j, kts)));
+  if constexpr (EM == 4) VR_TRY(full_corr_units(c, S.Bs, S.H.b, S.nb, S.joins, E));
+  return tail_units(E, S.nb, c.cfg.est_nseg, c.cfg.est_ratioA, S.H.a[0].has_nan != 0, S.H.b, nl,
+                    S.scores + p * c.lw, S.score_ld, viol, c.st, EM == 4 ? E.corr : nullptr);
+}
+
+// Every pass in the EST form of c.cfg, the flagged ones re-run in the exact form.
+// (Pre-joined units already hold their A positions: the EST walks, reading only those, skip
+// the join; an exact-form pass rewrites them with the same values beside the A chunks.)
+static int est_passes(const EngineCall& c, Solo& S) {
+  const EngineWs& E = S.E;
+  const int64_t inject = g_test_inject.load(std::memory_order_relaxed);
+  if (!c.cfg.prejoined) VR_TRY(join_units(c, S, JOIN_NONE));
+  const int64_t npass = c.npass();
   // The first EST pass runs alone: when the estimate cannot hold these A ranks (strongly
   // structured RDMs, giant tie groups) every pass is run in the exact form from there on.
-  for (int64_t p0 = pfirst, p1 = pfirst; p0 < npass; p0 = p1) {
-    p1 = std::min<int64_t>(npass, p0 == pfirst ? p0 + 1 : p0 + EST_MAX_PASSES);
-    VR_CHECK_HIP(hipMemsetAsync(E.viol, 0, (size_t)(p1 - p0) * sizeof(uint32_t), st));
-    VR_TRY(with_pass_tag(cfg.est_lds, lw == LANES, true, [&](auto tag) -> int {
-      using Tg = decltype(tag);
-      if constexpr (sizeof(typename Tg::tbt) == 2) {
-        for (int64_t p = p0; p < p1; ++p) {
-          const int64_t set0 = p * lw;
-          const int nl = (int)std::min<int64_t>(lw, total - set0);
-          VR_TRY(build_pass_masks(idx, k, set0, nl, full_first, E.masks, n, st));
-          VR_CHECK_HIP(hipMemsetAsync(E.queue, 0, sizeof(uint32_t) * (size_t)std::min<int64_t>(QS_RANKB + nb, QSLOTS),
-                                      st));  // this pass's work-queue counters
-          uint32_t* viol = E.viol + (p - p0);
-          auto run_pass = [&](auto em) -> int {
-            constexpr int EM = decltype(em)::value;
-            VR_TRY((bigA ? pass_a_est<EM, Tg::lds, Tg::full, true>(A, n, E, lw, nl, cfg, e3, viol, st)
-                         : pass_a_est<EM, Tg::lds, Tg::full, false>(A, n, E, lw, nl, cfg, e3, viol, st)));
-            if (p == inject) {
-              k_inject_tb<<<1, LANES, 0, st>>>(static_cast<uint16_t*>(E.TB), (uint32_t)(M / 2), lw, lw);
-              VR_CHECK_LAUNCH();
-            }
-            // EST 4: lane 0's ranks are stored shifted (est4_shift), so its B walks are the EST 3
-            // kernel (timed on their own slot) and k_full_corr supplies lane 0's shift sums
-            constexpr int EB = EM == 4 ? 3 : EM;
-            const int kts = EM == 4 ? KT_RANKB_FULL : -1;
-            for (int64_t j = 0; j < nb; ++j) {
-              const uint32_t* pj = joins[2 * j];  // EST walks read the A positions alone
-              VR_TRY((h[(size_t)j + 1].max_group >= 65536u
-                          ? walk_b<Tg::lds, Tg::full, uint16_t, true, EB>(Bs[j], pj, nullptr, n, E, lw, j, cfg, st, kts)
-                          : walk_b<Tg::lds, Tg::full, uint16_t, false, EB>(Bs[j], pj, nullptr, n, E, lw, j, cfg, st, kts)));
-              if constexpr (EM == 4) {
-                KtScope kt(KT_FULL_CORR, (double)M, st);
-                k_full_corr<<<CORR_BLK, 256, 0, st>>>(pj, Bs[j].gflag, Bs[j].gstart, h[(size_t)j + 1].G, M, e3.y,
-                                                  E.corr + (size_t)j * CORR_N);
-                VR_CHECK_LAUNCH();
-              }
-            }
-            return tail_units(E, nb, cfg.est_nseg, cfg.est_ratioA, h[0].has_nan != 0, nan_b, nl, scores + set0,
-                              score_ld, viol, st, EM == 4 ? E.corr : nullptr);
-          };
-          // EST 3 needs every lane to hold k stimuli: the pass holding the full set runs EST 4
-          const bool full0 = full_first && p == 0;
-          VR_TRY(cfg.est_mode == 3 ? (full0 ? run_pass(std::integral_constant<int, 4>{})
-                                            : run_pass(std::integral_constant<int, 3>{}))
-                                   : run_pass(std::integral_constant<int, 1>{}));
-        }
-      }
-      return VR_OK;
-    }));
-    std::vector<uint32_t> flags((size_t)(p1 - p0));
-    VR_CHECK_HIP(hipMemcpyAsync(flags.data(), E.viol, flags.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    VR_CHECK_HIP(hipStreamSynchronize(st));
+  for (int64_t p0 = 0, p1 = 0; p0 < npass; p0 = p1) {
+    p1 = std::min<int64_t>(npass, p0 == 0 ? 1 : p0 + EST_MAX_PASSES);
+    VR_CHECK_HIP(hipMemsetAsync(E.viol, 0, (size_t)(p1 - p0) * sizeof(uint32_t), c.st));
     for (int64_t p = p0; p < p1; ++p) {
-      if (!flags[(size_t)(p - p0)]) continue;
-      // only the tail invariants flagged it: the A walk's window checks passed, so the B side
-      // recovered a wrong rank (an A-flagged pass breaks the invariants too, as expected)
-      if ((flags[(size_t)(p - p0)] & 3u) == 2u) g_est_tail_flags.fetch_add(1);
-      if (second != JOIN_CHUNK) VR_TRY(join(JOIN_CHUNK));
-      g_est_reruns.fetch_add(1);
-      const int64_t set0 = p * lw;
-      const int nl = (int)std::min<int64_t>(lw, total - set0);
-      VR_TRY(with_pass_tag(cfg.use_lds, lw == LANES, narrow, [&](auto tag) { return exact_pass(tag, set0, nl); }));
+      uint32_t* viol = E.viol + (p - p0);
+      const int inj = p == inject ? c.lw : 0;
+      VR_TRY(build_pass_masks(c.idx, c.k, p * c.lw, c.nl(p), c.full_first, E.masks, c.n, c.st));
+      VR_TRY(with_pass_tag(c.cfg.est_lds, c.lw == LANES, true, [&](auto tag) -> int {
+        using Tg = decltype(tag);
+        return c.cfg.est_mode == 3 ? (c.full0(p) ? est_pass<4, Tg::lds, Tg::full>(c, S, p, viol, inj)
+                                                 : est_pass<3, Tg::lds, Tg::full>(c, S, p, viol, inj))
+                                   : est_pass<1, Tg::lds, Tg::full>(c, S, p, viol, inj);
+      }));
     }
-    if (p0 == pfirst && flags[0] && p1 < npass) return exact_from(p1 * lw);  // give up on the estimate
+    std::vector<int64_t> flagged;
+    VR_TRY(harvest_flags(c, E, p0, p1 - p0, true, flagged));
+    VR_TRY(exact_passes(c, S, flagged));
+    if (p0 == 0 && !flagged.empty()) return exact_from(c, S, p1);  // give up on the estimate
   }
   return VR_OK;
 }
 
-// run_engine_multi_impl, then the exact-form passes' invariant flag: a set flag means the
-// exact arithmetic itself went wrong, so the call fails instead of returning the scores.
-static int run_engine_multi(const PlanView& A, const PlanView* Bs, int64_t nb, int64_t n,
-                            const int32_t* idx, int64_t k, int64_t n_sets, int full_first,
-                            double* scores, int64_t score_ld, uint32_t* const* joins,
-                            const EngineWs& E, int lw, const EngineCfg& cfg, hipStream_t st,
-                            const std::vector<int64_t>* exact_passes = nullptr) {
+static int run_solo(const EngineCall& c, Solo& S) {
+  if (c.total == 0 || S.nb == 0) return VR_OK;
+  if (c.M == 0) {  // no pairs: every score is NaN (scipy on empty input)
+    for (int64_t j = 0; j < S.nb; ++j) {
+      k_fill_nan<<<(unsigned)((c.total + 255) / 256), 256, 0, c.st>>>(S.scores + j * S.score_ld, c.total);
+      VR_CHECK_LAUNCH();
+    }
+    return VR_OK;
+  }
+  VR_TRY(solo_begin(c, S));
+  if (!c.cfg.env.est) return exact_from(c, S, 0);
+  bool predicted_bad = false;
+  VR_TRY(solo_check(c, S, predicted_bad));
+  if (!predicted_bad) return est_passes(c, S);
+  // The lane-uniform EST 3 window cannot hold these counts (per-stimulus structure moves a
+  // subset's included count further from the line than 2^14 pairs: it grows ~ n^1.5, so
+  // large triangles cross it first). EST 1 follows each lane's own counts (an interpolated
+  // table whose knots are the lane's counts at <= 144 boundaries, one LDS read per pair),
+  // one gather per pair like EST 3; its flagged passes are re-run exact as ever. The exact
+  // form from the start only with VISREPS_ENGINE_EST1_FALLBACK=0 or a point-only call.
+  // (Only where the exact form reads its masks from L2 too, n > 20,352: below that the exact
+  // walks keep the masks in LDS and EST 1, whose table takes that LDS, measured slower --
+  // 79 vs 73 ms per unit on bench.structured_est_probe's RDM at N = 10k; at 20,500 EST 1
+  // won, 215 vs 234 ms, profiles/r6_large_n_probe_v2.log.)
+  if (c.lw == LANES && !c.cfg.use_lds && c.cfg.env.est1_fallback) {
+    EngineCall c1 = c;
+    c1.cfg = engine_cfg(c.n, c.cfg.env, 1);
+    c1.cfg.prejoined = c.cfg.prejoined;
+    if (c1.cfg.nwaves == c.cfg.nwaves && c1.cfg.est_nsegA <= (uint32_t)c.cfg.nwaves * SEGS_PER_WAVE) {
+      g_est1_fallbacks.fetch_add(1);
+      VR_TRY(solo_begin(c1, S));  // again: the segment tables for c1's segment counts
+      return est_passes(c1, S);
+    }
+  }
+  return exact_from(c, S, 0);
+}
+
+// One region's run -- the whole call (run_solo), or only the passes `only` in the exact form
+// -- then the exact-form passes' invariant flag: a set flag means the exact arithmetic itself
+// went wrong, so the call fails instead of returning the scores.
+static int run_engine_multi(const EngineCall& c, const PlanView& A, const PlanView* Bs, int64_t nb, double* scores,
+                            int64_t score_ld, uint32_t* const* joins, const EngineWs& E,
+                            const std::vector<int64_t>* only = nullptr) {
   uint32_t* const xbad = E.viol + EST_MAX_PASSES;
-  VR_CHECK_HIP(hipMemsetAsync(xbad, 0, sizeof(uint32_t), st));
-  VR_TRY(run_engine_multi_impl(A, Bs, nb, n, idx, k, n_sets, full_first, scores, score_ld, joins, E, lw, cfg, st,
-                               exact_passes));
+  VR_CHECK_HIP(hipMemsetAsync(xbad, 0, sizeof(uint32_t), c.st));
+  Solo S{A, Bs, nb, scores, score_ld, joins, E};
+  if (only) VR_TRY(solo_begin(c, S));
+  VR_TRY(only ? exact_passes(c, S, *only) : run_solo(c, S));
   uint32_t bad = 0;
-  VR_CHECK_HIP(hipMemcpyAsync(&bad, xbad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  VR_CHECK_HIP(hipStreamSynchronize(st));
+  VR_CHECK_HIP(hipMemcpyAsync(&bad, xbad, sizeof(uint32_t), hipMemcpyDeviceToHost, c.st));
+  VR_CHECK_HIP(hipStreamSynchronize(c.st));
   if (bad) {
     set_error("bootstrap engine: an exact-form pass broke the rank-sum invariants (included pairs / sum of ranks)");
     return VR_EINTERNAL;
@@ -2141,17 +2234,6 @@ static int run_engine_multi(const PlanView& A, const PlanView* Bs, int64_t nb, i
   return VR_OK;
 }
 
-// R A plans (regions) x nb B plans (model layers), every unit pre-joined (joins[r][2 j] =
-// unit (j, r)'s A positions; joins[r][2 j + 1] = region 0's second arrays): scores of unit
-// (j, r) at scores + (r nb + j) score_ld. The EST passes run region-fused (k_rankB_grid: one
-// B walk per B plan for all fused regions) on the happy path -- EST 3 with its 4 form for
-// the full set, B tie groups < 2^16 -- for every region with A tie groups < 2^16 whose
-// estimate passes its up-front check; a region failing that, or one whose pass is later
-// flagged, leaves the fused set and runs on its own once the fused passes are done (EST with
-// exact re-runs of its flagged passes, or the exact form), so the other regions stay fused.
-// Es[0]: region 0's full workspace (multi_layout, prejoined), which also holds the shared
-// masks and B segment tables and serves every region run on its own; Es[1..]: slim
-// workspaces (u16 TB, no join arrays) beside it.
 template <bool LDS>
 static int launch_grid(int R, unsigned grid, size_t lds, const PlanView& B, const uint64_t* masks, int64_t n,
                        const GridB& g, uint32_t ns, const uint2* ftab, const uint32_t* segpos, uint32_t* q,
@@ -2168,31 +2250,29 @@ static int launch_grid(int R, unsigned grid, size_t lds, const PlanView& B, cons
   return VR_OK;
 }
 
-// masks of the grid walk in LDS (one 16-wave workgroup per CU: up to 20,352 stimuli);
-// VISREPS_ENGINE_GRID_LDS=0 reads them from L2 at any n (A/B, tests)
-static bool grid_masks_lds(int64_t n) {
-  return (size_t)n * sizeof(uint64_t) <= 160 * 1024 - 1024 && env_int("VISREPS_ENGINE_GRID_LDS", 1) != 0;
-}
-
-static int run_engine_grid(const PlanView* As, int R, const PlanView* Bs, int64_t nb, int64_t n, const int32_t* idx,
-                           int64_t k, int64_t n_sets, int full_first, double* scores, int64_t score_ld,
-                           uint32_t* const* const* joins, const EngineWs* Es, const EngineCfg& cfg, hipStream_t st) {
-  const int64_t M = pairs_of(n);
-  const int64_t total = n_sets + (full_first ? 1 : 0);
+// R A plans (regions) x nb B plans (model layers), every unit pre-joined (joins[r][2 j] =
+// unit (j, r)'s A positions; joins[r][2 j + 1] = region 0's second arrays): scores of unit
+// (j, r) at scores + (r nb + j) score_ld. The EST passes run region-fused (k_rankB_grid: one
+// B walk per B plan for all fused regions) on the happy path -- EST 3 with its 4 form for
+// the full set, B tie groups < 2^16 -- for every region with A tie groups < 2^16 whose
+// estimate passes its up-front check; a region failing that, or one whose pass is later
+// flagged, leaves the fused set and runs on its own once the fused passes are done (EST with
+// exact re-runs of its flagged passes, or the exact form), so the other regions stay fused.
+// Es[0]: region 0's full workspace (multi_layout, prejoined), which also holds the shared
+// masks and B segment tables and serves every region run on its own; Es[1..]: slim
+// workspaces (u16 TB, no join arrays) beside it.
+static int run_engine_grid(const EngineCall& c, const PlanView* As, int R, const PlanView* Bs, int64_t nb,
+                           double* scores, int64_t score_ld, uint32_t* const* const* joins, const EngineWs* Es) {
   std::vector<int> solo;  // regions run on their own once the fused passes are done
   std::vector<std::vector<int64_t>> fix((size_t)R);  // fused regions' flagged passes (re-run exact)
-  std::vector<PlanHeader> hA((size_t)R), hB((size_t)nb);
-  std::vector<char> nan_b((size_t)nb);
   std::vector<EngineWs> E(Es, Es + R);  // the masks of a pass are built once (region 0's buffer)
   for (int r = 1; r < R; ++r) E[(size_t)r].masks = E[0].masks;
+  auto region_scores = [&](int r) { return scores + (size_t)r * nb * score_ld; };
   auto finish = [&]() -> int {
-    for (int r : solo)
-      VR_TRY(run_engine_multi(As[r], Bs, nb, n, idx, k, n_sets, full_first, scores + (size_t)r * nb * score_ld,
-                              score_ld, joins[r], Es[0], LANES, cfg, st));
+    for (int r : solo) VR_TRY(run_engine_multi(c, As[r], Bs, nb, region_scores(r), score_ld, joins[r], Es[0]));
     for (int r = 0; r < R; ++r)
       if (!fix[(size_t)r].empty())
-        VR_TRY(run_engine_multi(As[r], Bs, nb, n, idx, k, n_sets, full_first, scores + (size_t)r * nb * score_ld,
-                                score_ld, joins[r], Es[0], LANES, cfg, st, &fix[(size_t)r]));
+        VR_TRY(run_engine_multi(c, As[r], Bs, nb, region_scores(r), score_ld, joins[r], Es[0], &fix[(size_t)r]));
     return VR_OK;
   };
   auto all_solo = [&]() -> int {
@@ -2200,86 +2280,61 @@ static int run_engine_grid(const PlanView* As, int R, const PlanView* Bs, int64_
     for (int r = 0; r < R; ++r) solo.push_back(r);
     return finish();
   };
-  if (total == 0 || nb == 0 || M == 0) return all_solo();
-  for (int r = 0; r < R; ++r)
-    VR_CHECK_HIP(hipMemcpyAsync(&hA[(size_t)r], As[r].hdr, sizeof(PlanHeader), hipMemcpyDeviceToHost, st));
-  for (int64_t j = 0; j < nb; ++j)
-    VR_CHECK_HIP(hipMemcpyAsync(&hB[(size_t)j], Bs[j].hdr, sizeof(PlanHeader), hipMemcpyDeviceToHost, st));
-  VR_CHECK_HIP(hipStreamSynchronize(st));
-  for (int64_t j = 0; j < nb; ++j) nan_b[(size_t)j] = hB[(size_t)j].has_nan != 0;
-  bool b_small = true;  // B tie groups < 2^16 (the fused walks' 64-bit tie sums)
-  for (int64_t j = 0; j < nb; ++j) b_small = b_small && hB[(size_t)j].max_group < 65536u;
-  if (!engine_est()) return all_solo();  // every pass exact: the per-region calls
-  const bool fused = cfg.est_mode == 3 && R >= 2 && R <= 4 && env_int("VISREPS_ENGINE_GRID", 1) != 0 && b_small;
+  if (c.total == 0 || nb == 0 || c.M == 0) return all_solo();
+  Headers H;
+  VR_TRY(fetch_headers(As, R, Bs, nb, c.st, H));
+  // every pass exact, EST 1, one region, VISREPS_ENGINE_GRID=0, giant B tie groups: the per-region calls
+  if (!c.cfg.env.est || c.cfg.est_mode != 3 || R < 2 || R > 4 || !c.cfg.env.grid || !H.b_small) return all_solo();
   // test hook (vr_test_engine_inject): the first fused region's TB gets the B-side error after
   // its A walk of that pass, so the region must be flagged and re-run on its own
   const int64_t inject = g_test_inject.load(std::memory_order_relaxed);
-  if (!fused) return all_solo();
   std::vector<int> act;  // the fused regions
-  for (int r = 0; r < R; ++r) (hA[(size_t)r].max_group < 65536u ? act : solo).push_back(r);
-  // (a point-only call holds the full set alone: its window is the full set's, so lane 0's
-  // EST 4 shift is at most 1 -- with k's window instead a group of > 3 tied pairs could
-  // shift below 1 and flag the pass)
-  const uint2 e3 = est3_params(n_sets > 0 ? k : n, M);
-  const uint32_t ns = cfg.est_nseg, nsA = cfg.est_nsegA;
+  for (int r = 0; r < R; ++r) (H.a[(size_t)r].max_group < 65536u ? act : solo).push_back(r);
   // A-side walks: masks in LDS when two 16-wave workgroups per CU hold them (n <= 10,176),
   // else from L2 (the per-region calls' choice, engine_cfg)
   auto est_a = [&](auto&& fn) -> int {
-    return cfg.est_lds ? fn(std::integral_constant<bool, true>{}) : fn(std::integral_constant<bool, false>{});
+    return c.cfg.est_lds ? fn(std::integral_constant<bool, true>{}) : fn(std::integral_constant<bool, false>{});
   };
-  for (int r : act) {
-    k_seg_table<<<(nsA + 256) / 256, 256, 0, st>>>(As[r].gstart, As[r].hdr, M, nsA, E[(size_t)r].segposA);
-    VR_CHECK_LAUNCH();
-  }
-  for (int64_t j = 0; j < nb; ++j) {  // B segments depend on the B plan only: region 0's table
-    k_seg_table<<<(ns + 256) / 256, 256, 0, st>>>(Bs[j].gstart, Bs[j].hdr, M, ns, E[0].segposB + E[0].segstride * (size_t)j);
-    VR_CHECK_LAUNCH();
-  }
-  // the up-front estimate check, per region (its counts are its own)
-  if (n_sets > 0 && env_int("VISREPS_ENGINE_EST_PREDICT", 1) != 0) {
-    const int nl0 = (int)std::min<int64_t>(LANES, total);
-    VR_TRY(build_pass_masks(idx, k, 0, nl0, full_first, E[0].masks, n, st));
-    std::vector<int> keep, pbad;
+  for (int r : act) VR_TRY(seg_table_a(c, As[r], E[(size_t)r]));
+  VR_TRY(seg_tables_b(c, Bs, nb, E[0]));
+  // the up-front estimate check, per region (its counts are its own). Regions off the
+  // estimate run on their own, where run_solo repeats the check, counts it and picks the
+  // exact form or EST 1
+  if (est_check_on(c)) {
+    VR_TRY(build_pass_masks(c.idx, c.k, 0, c.nl(0), c.full_first, E[0].masks, c.n, c.st));
+    std::vector<int> keep;
     for (int r : act) {
       bool bad = false;
       VR_TRY(est_a([&](auto cl) -> int {
-        return est_predict<decltype(cl)::value, true>(As[r], n, E[(size_t)r], LANES, nl0, full_first != 0, cfg, e3,
-                                                      st, bad);
+        return est_check<decltype(cl)::value, true>(c, As[r], E[(size_t)r], false, bad);
       }));
-      (bad ? pbad : keep).push_back(r);
+      (bad ? solo : keep).push_back(r);
     }
     act.swap(keep);
-    // Regions off the estimate run on their own, where run_engine_multi repeats the check,
-    // counts it and picks the exact form or EST 1
-    for (int r : pbad) solo.push_back(r);
   }
   if (act.size() < 2) return all_solo();  // fusing pays with two regions or more
-  const int64_t npass = (total + LANES - 1) / LANES;
+  const int64_t npass = c.npass();
   const unsigned ggrid = (unsigned)num_cus();  // one 16-wave workgroup per CU (4 waves per SIMD)
-  const bool glds = grid_masks_lds(n);
+  // masks of the grid walk in LDS (one 16-wave workgroup per CU: up to 20,352 stimuli)
+  const bool glds = (size_t)c.n * sizeof(uint64_t) <= 160 * 1024 - 1024 && c.cfg.env.grid_lds;
   for (int r : act)
-    VR_CHECK_HIP(hipMemsetAsync(E[(size_t)r].viol, 0, (size_t)std::min<int64_t>(npass, EST_MAX_PASSES) * sizeof(uint32_t), st));
+    VR_CHECK_HIP(hipMemsetAsync(E[(size_t)r].viol, 0, (size_t)std::min<int64_t>(npass, EST_MAX_PASSES) * sizeof(uint32_t), c.st));
   for (int64_t p = 0; p < npass; ++p) {
-    const int64_t set0 = p * LANES;
-    const int nl = (int)std::min<int64_t>(LANES, total - set0);
-    const bool full0 = full_first && p == 0;
+    const int nl = c.nl(p);
+    const bool full0 = c.full0(p);
     const int64_t vslot = p % EST_MAX_PASSES;
-    VR_TRY(build_pass_masks(idx, k, set0, nl, full_first, E[0].masks, n, st));
+    VR_TRY(build_pass_masks(c.idx, c.k, p * LANES, nl, c.full_first, E[0].masks, c.n, c.st));
     for (int r : act) {
-      VR_CHECK_HIP(hipMemsetAsync(E[(size_t)r].queue, 0, sizeof(uint32_t) * (size_t)QS_RANKB, st));
-      uint32_t* viol = E[(size_t)r].viol + vslot;
+      const EngineWs& e = E[(size_t)r];
+      const int inj = p == inject && r == act[0] ? nl : 0;
       VR_TRY(est_a([&](auto cl) -> int {
         constexpr bool CL = decltype(cl)::value;
-        return full0 ? pass_a_est<4, CL, true, false>(As[r], n, E[(size_t)r], LANES, nl, cfg, e3, viol, st)
-                     : pass_a_est<3, CL, true, false>(As[r], n, E[(size_t)r], LANES, nl, cfg, e3, viol, st);
+        return full0 ? pass_a_est<4, CL, true, false>(c, As[r], e, nl, 0, e.viol + vslot, inj)
+                     : pass_a_est<3, CL, true, false>(c, As[r], e, nl, 0, e.viol + vslot, inj);
       }));
-      if (p == inject && r == act[0]) {
-        k_inject_tb<<<1, LANES, 0, st>>>(static_cast<uint16_t*>(E[(size_t)r].TB), (uint32_t)(M / 2), LANES, nl);
-        VR_CHECK_LAUNCH();
-      }
     }
     VR_CHECK_HIP(hipMemsetAsync(E[0].queue + QS_RANKB, 0,
-                                sizeof(uint32_t) * (size_t)std::min<int64_t>(nb, QSLOTS - QS_RANKB), st));
+                                sizeof(uint32_t) * (size_t)std::min<int64_t>(nb, QSLOTS - QS_RANKB), c.st));
     const int RA = (int)act.size();
     for (int64_t j = 0; j < nb; ++j) {
       GridB g{};
@@ -2291,31 +2346,21 @@ static int run_engine_grid(const PlanView* As, int R, const PlanView* Bs, int64_
         g.seg_tot[i] = e.segB_tot + us;
         g.seg_part[i] = e.segB_part + us * PB_N;
       }
-      uint32_t* q = E[0].queue + QS_RANKB + (size_t)j % (size_t)(QSLOTS - QS_RANKB);
-      if (j >= QSLOTS - QS_RANKB) VR_CHECK_HIP(hipMemsetAsync(q, 0, sizeof(uint32_t), st));
-      const uint32_t* segpos = E[0].segposB + E[0].segstride * (size_t)j;
+      const uint32_t* segpos = nullptr;
+      uint32_t* q = nullptr;
+      VR_TRY(est_slot_b(E[0], j, c.st, segpos, q));
       // the window parameters of this pass (k_c0_u: the same for every region) from a fused
       // region's workspace: region 0 may be running on its own
       const uint2* ftab = E[(size_t)act[0]].ftab;
-      KtScope kt(full0 ? KT_RANKB_FULL : KT_RANKB_GRID, (double)M * RA, st);
-      if (glds)
-        VR_TRY(launch_grid<true>(RA, ggrid, (size_t)n * sizeof(uint64_t), Bs[j], E[0].masks, n, g, ns, ftab,
-                                 segpos, q, st));
-      else
-        VR_TRY(launch_grid<false>(RA, ggrid, 0, Bs[j], E[0].masks, n, g, ns, ftab, segpos, q, st));
+      KtScope kt(full0 ? KT_RANKB_FULL : KT_RANKB_GRID, (double)c.M * RA, c.st);
+      VR_TRY((glds ? launch_grid<true> : launch_grid<false>)(RA, ggrid, glds ? (size_t)c.n * sizeof(uint64_t) : 0, Bs[j],
+                                                             E[0].masks, c.n, g, c.cfg.est_nseg, ftab, segpos, q, c.st));
     }
     for (int r : act) {
-      if (full0) {
-        for (int64_t j = 0; j < nb; ++j) {
-          KtScope kt(KT_FULL_CORR, (double)M, st);
-          k_full_corr<<<CORR_BLK, 256, 0, st>>>(joins[r][2 * j], Bs[j].gflag, Bs[j].gstart, hB[(size_t)j].G, M, e3.y,
-                                                E[(size_t)r].corr + (size_t)j * CORR_N);
-          VR_CHECK_LAUNCH();
-        }
-      }
-      VR_TRY(tail_units(E[(size_t)r], nb, ns, cfg.est_ratioA, hA[(size_t)r].has_nan != 0, nan_b, nl,
-                        scores + (size_t)r * nb * score_ld + set0, score_ld, E[(size_t)r].viol + vslot, st,
-                        full0 ? E[(size_t)r].corr : nullptr));
+      const EngineWs& e = E[(size_t)r];
+      if (full0) VR_TRY(full_corr_units(c, Bs, H.b, nb, joins[r], e));
+      VR_TRY(tail_units(e, nb, c.cfg.est_nseg, c.cfg.est_ratioA, H.a[(size_t)r].has_nan != 0, H.b, nl,
+                        region_scores(r) + p * LANES, score_ld, e.viol + vslot, c.st, full0 ? e.corr : nullptr));
     }
     // flags: after the first pass, then every EST_MAX_PASSES passes and at the end. A region
     // whose first pass is flagged (its estimate is off: structured counts, giant tie groups)
@@ -2324,24 +2369,11 @@ static int run_engine_grid(const PlanView* As, int R, const PlanView* Bs, int64_
     // strayed) is re-run alone in the exact form at the end, the region staying fused. The
     // other regions' sums are their own and stand.
     if (p == 0 || vslot == EST_MAX_PASSES - 1 || p == npass - 1) {
-      const int64_t cnt = vslot + 1, pbase = p - vslot;
       std::vector<int> keep;
       for (int r : act) {
-        std::vector<uint32_t> flags((size_t)cnt);
-        VR_CHECK_HIP(hipMemcpyAsync(flags.data(), E[(size_t)r].viol, flags.size() * sizeof(uint32_t),
-                                    hipMemcpyDeviceToHost, st));
-        VR_CHECK_HIP(hipStreamSynchronize(st));
-        if (p == 0 && flags[0]) {
-          solo.push_back(r);
-          continue;
-        }
-        for (int64_t i = 0; i < cnt; ++i) {
-          if (!flags[(size_t)i]) continue;
-          fix[(size_t)r].push_back(pbase + i);
-          g_est_reruns.fetch_add(1);
-          if ((flags[(size_t)i] & 3u) == 2u) g_est_tail_flags.fetch_add(1);
-        }
-        keep.push_back(r);
+        std::vector<int64_t> first;  // the first pass, flagged: not to fix, the region leaves
+        VR_TRY(harvest_flags(c, E[(size_t)r], p - vslot, vslot + 1, p != 0, p == 0 ? first : fix[(size_t)r]));
+        (first.empty() ? keep : solo).push_back(r);
       }
       act.swap(keep);
       if (act.size() < 2 && p + 1 < npass) {  // one region left: it runs on its own too
@@ -2354,19 +2386,17 @@ static int run_engine_grid(const PlanView* As, int R, const PlanView* Bs, int64_
       }
       if (vslot == EST_MAX_PASSES - 1 && p + 1 < npass)
         for (int r : act)
-          VR_CHECK_HIP(hipMemsetAsync(E[(size_t)r].viol, 0, (size_t)EST_MAX_PASSES * sizeof(uint32_t), st));
+          VR_CHECK_HIP(hipMemsetAsync(E[(size_t)r].viol, 0, (size_t)EST_MAX_PASSES * sizeof(uint32_t), c.st));
     }
   }
   std::sort(solo.begin(), solo.end());
   return finish();
 }
 
-// Scores for `total` subsets (full set first if full_first), 64 per pass.
-static int run_engine(const PlanView& A, const PlanView& B, int64_t n, const int32_t* idx,
-                      int64_t k, int64_t n_sets, int full_first, double* scores,
-                      const EngineWs& E, int lw, const EngineCfg& cfg, hipStream_t st) {
+// Scores for `total` subsets (full set first if full_first), lw per pass.
+static int run_engine(const EngineCall& c, const PlanView& A, const PlanView& B, double* scores, const EngineWs& E) {
   uint32_t* joins[2] = {E.posA_byB, E.chunkA_byB};
-  return run_engine_multi(A, &B, 1, n, idx, k, n_sets, full_first, scores, 0, joins, E, lw, cfg, st);
+  return run_engine_multi(c, A, &B, 1, scores, 0, joins, E);
 }
 
 // Workspace of the multi-B engine: the engine scratch, then the joins of B 1..nb-1 (B 0
@@ -2429,6 +2459,35 @@ int vr_test_engine_inject(int64_t pass) {
   return VR_OK;
 }
 
+// Argument check of the plan entry points (fn: the entry point's name). n_a / n_b: 1 where it takes
+// a single plan; ptrs_ok: its own required pointers are there; need_ld: the score rows must hold
+// all `total` subsets; planAs / planBs: the plan arrays whose entries are checked (null: none).
+static int check_args(const char* fn, int64_t n, int64_t n_a, int64_t n_b, bool ptrs_ok, const int32_t* idx, int64_t k,
+                      int64_t n_sets, int full_first, bool need_ld, int64_t ld_scores, const void* const* planAs,
+                      const void* const* planBs) {
+  VR_REQUIRE(n >= 0 && n <= 65535, "%s: n=%lld out of range", fn, (long long)n);
+  VR_REQUIRE(n_a >= 1 && n_a <= 4, "%s: n_a=%lld not in [1, 4]", fn, (long long)n_a);
+  VR_REQUIRE(n_b >= 0, "%s: n_b=%lld", fn, (long long)n_b);
+  VR_REQUIRE(ptrs_ok, "%s: null pointer", fn);
+  VR_REQUIRE(k >= 0 && k <= n && n_sets >= 0, "%s: bad k=%lld sets=%lld", fn, (long long)k, (long long)n_sets);
+  VR_REQUIRE(idx != nullptr || n_sets == 0 || k == 0, "%s: null idx", fn);
+  const int64_t total = n_sets + (full_first ? 1 : 0);
+  VR_REQUIRE(!need_ld || ld_scores >= total, "%s: ld_scores %lld < %lld", fn, (long long)ld_scores, (long long)total);
+  for (int64_t i = 0; planAs && i < n_a; ++i) VR_REQUIRE(planAs[i] != nullptr, "%s: planAs[%lld] is null", fn, (long long)i);
+  for (int64_t j = 0; planBs && j < n_b; ++j) VR_REQUIRE(planBs[j] != nullptr, "%s: planBs[%lld] is null", fn, (long long)j);
+  return VR_OK;
+}
+static int check_ws(const char* fn, const void* ws, size_t ws_bytes, size_t need) {
+  if (ws_bytes >= need && ws != nullptr) return VR_OK;
+  set_error("%s: workspace %zu < %zu", fn, ws_bytes, need);
+  return VR_EWORKSPACE;
+}
+static std::vector<PlanView> plan_views(const void* const* plans, int64_t count, int64_t n) {
+  std::vector<PlanView> v;
+  for (int64_t j = 0; j < count; ++j) v.push_back(plan_layout(const_cast<void*>(plans[j]), n));
+  return v;
+}
+
 size_t vr_bootstrap_workspace(int64_t n) {
   size_t b = 0;
   n = n < 0 ? 0 : n;
@@ -2439,21 +2498,15 @@ size_t vr_bootstrap_workspace(int64_t n) {
 int vr_bootstrap_spearman_plans(const void* planA, const void* planB, int64_t n,
                                 const int32_t* idx, int64_t k, int64_t n_sets, int full_first,
                                 double* scores, void* ws, size_t ws_bytes, void* stream) {
-  VR_REQUIRE(n >= 0 && n <= 65535, "vr_bootstrap_spearman_plans: n=%lld out of range", (long long)n);
-  VR_REQUIRE(planA && planB && scores, "vr_bootstrap_spearman_plans: null pointer");
-  VR_REQUIRE(k >= 0 && k <= n && n_sets >= 0, "vr_bootstrap_spearman_plans: bad k=%lld sets=%lld",
-             (long long)k, (long long)n_sets);
-  VR_REQUIRE(idx != nullptr || n_sets == 0 || k == 0, "vr_bootstrap_spearman_plans: null idx");
+  const char* fn = "vr_bootstrap_spearman_plans";
+  VR_TRY(check_args(fn, n, 1, 1, planA && planB && scores, idx, k, n_sets, full_first, false, 0, nullptr, nullptr));
   const EngineCfg cfg = engine_cfg(n);
   size_t need = 0;
   EngineWs E = engine_layout(ws, n, LANES, cfg.nwaves, &need);
-  if (ws_bytes < need || ws == nullptr) {
-    set_error("vr_bootstrap_spearman_plans: workspace %zu < %zu", ws_bytes, need);
-    return VR_EWORKSPACE;
-  }
+  VR_TRY(check_ws(fn, ws, ws_bytes, need));
   PlanView A = plan_layout(const_cast<void*>(planA), n);
   PlanView B = plan_layout(const_cast<void*>(planB), n);
-  return run_engine(A, B, n, idx, k, n_sets, full_first, scores, E, LANES, cfg, as_stream(stream));
+  return run_engine(engine_call(n, idx, k, n_sets, full_first, LANES, cfg, stream), A, B, scores, E);
 }
 
 size_t vr_bootstrap_multi_workspace(int64_t n, int64_t n_b) {
@@ -2462,35 +2515,33 @@ size_t vr_bootstrap_multi_workspace(int64_t n, int64_t n_b) {
   return multi_layout(nullptr, n, n_b, engine_cfg(n).nwaves, nullptr, nullptr);
 }
 
+// vr_bootstrap_spearman_multi and, with every unit's A positions in posA (joined), _multi_joined
+static int multi_entry(const char* fn, bool joined, const void* planA, const void* const* planBs, int64_t n_b,
+                       int64_t n, const int32_t* idx, int64_t k, int64_t n_sets, int full_first, double* scores,
+                       int64_t ld_scores, uint32_t* const* posA, void* ws, size_t ws_bytes, void* stream) {
+  VR_TRY(check_args(fn, n, 1, n_b, planA && (n_b == 0 || (planBs && scores)), idx, k, n_sets, full_first, n_b > 1,
+                    ld_scores, nullptr, planBs));
+  VR_REQUIRE(!joined || n_b == 0 || posA != nullptr, "%s: null posA", fn);
+  for (int64_t j = 0; joined && j < n_b; ++j) VR_REQUIRE(posA[j] != nullptr, "%s: posA[%lld] is null", fn, (long long)j);
+  EngineCfg cfg = engine_cfg(n);
+  cfg.prejoined = joined;
+  VR_TRY(check_ws(fn, ws, ws_bytes, multi_layout(nullptr, n, n_b, cfg.nwaves, nullptr, nullptr, joined)));
+  EngineWs E;
+  std::vector<uint32_t*> joins;
+  multi_layout(ws, n, n_b, cfg.nwaves, &E, &joins, joined);
+  for (int64_t j = 0; joined && j < n_b; ++j) joins[(size_t)(2 * j)] = posA[j];
+  const PlanView A = plan_layout(const_cast<void*>(planA), n);
+  const std::vector<PlanView> Bs = plan_views(planBs, n_b, n);
+  return run_engine_multi(engine_call(n, idx, k, n_sets, full_first, LANES, cfg, stream), A, Bs.data(), n_b, scores,
+                          ld_scores, joins.data(), E);
+}
+
 int vr_bootstrap_spearman_multi(const void* planA, const void* const* planBs, int64_t n_b, int64_t n,
                                 const int32_t* idx, int64_t k, int64_t n_sets, int full_first,
                                 double* scores, int64_t ld_scores, void* ws, size_t ws_bytes,
                                 void* stream) {
-  VR_REQUIRE(n >= 0 && n <= 65535, "vr_bootstrap_spearman_multi: n=%lld out of range", (long long)n);
-  VR_REQUIRE(n_b >= 0, "vr_bootstrap_spearman_multi: n_b=%lld", (long long)n_b);
-  VR_REQUIRE(planA && (n_b == 0 || (planBs && scores)), "vr_bootstrap_spearman_multi: null pointer");
-  VR_REQUIRE(k >= 0 && k <= n && n_sets >= 0, "vr_bootstrap_spearman_multi: bad k=%lld sets=%lld",
-             (long long)k, (long long)n_sets);
-  VR_REQUIRE(idx != nullptr || n_sets == 0 || k == 0, "vr_bootstrap_spearman_multi: null idx");
-  const int64_t total = n_sets + (full_first ? 1 : 0);
-  VR_REQUIRE(n_b <= 1 || ld_scores >= total, "vr_bootstrap_spearman_multi: ld_scores %lld < %lld",
-             (long long)ld_scores, (long long)total);
-  for (int64_t j = 0; j < n_b; ++j)
-    VR_REQUIRE(planBs[j] != nullptr, "vr_bootstrap_spearman_multi: planBs[%lld] is null", (long long)j);
-  const EngineCfg cfg = engine_cfg(n);
-  const size_t need = multi_layout(nullptr, n, n_b, cfg.nwaves, nullptr, nullptr);
-  if (ws_bytes < need || ws == nullptr) {
-    set_error("vr_bootstrap_spearman_multi: workspace %zu < %zu", ws_bytes, need);
-    return VR_EWORKSPACE;
-  }
-  EngineWs E;
-  std::vector<uint32_t*> joins;
-  multi_layout(ws, n, n_b, cfg.nwaves, &E, &joins);
-  const PlanView A = plan_layout(const_cast<void*>(planA), n);
-  std::vector<PlanView> Bs;
-  for (int64_t j = 0; j < n_b; ++j) Bs.push_back(plan_layout(const_cast<void*>(planBs[j]), n));
-  return run_engine_multi(A, Bs.data(), n_b, n, idx, k, n_sets, full_first, scores, ld_scores,
-                          joins.data(), E, LANES, cfg, as_stream(stream));
+  return multi_entry("vr_bootstrap_spearman_multi", false, planA, planBs, n_b, n, idx, k, n_sets, full_first, scores,
+                     ld_scores, nullptr, ws, ws_bytes, stream);
 }
 
 size_t vr_bootstrap_multi_joined_workspace(int64_t n, int64_t n_b) {
@@ -2503,36 +2554,8 @@ int vr_bootstrap_spearman_multi_joined(const void* planA, const void* const* pla
                                 const int32_t* idx, int64_t k, int64_t n_sets, int full_first,
                                 double* scores, int64_t ld_scores, uint32_t* const* posA, void* ws,
                                 size_t ws_bytes, void* stream) {
-  VR_REQUIRE(n >= 0 && n <= 65535, "vr_bootstrap_spearman_multi_joined: n=%lld out of range", (long long)n);
-  VR_REQUIRE(n_b >= 0, "vr_bootstrap_spearman_multi_joined: n_b=%lld", (long long)n_b);
-  VR_REQUIRE(planA && (n_b == 0 || (planBs && scores)), "vr_bootstrap_spearman_multi_joined: null pointer");
-  VR_REQUIRE(k >= 0 && k <= n && n_sets >= 0, "vr_bootstrap_spearman_multi_joined: bad k=%lld sets=%lld",
-             (long long)k, (long long)n_sets);
-  VR_REQUIRE(idx != nullptr || n_sets == 0 || k == 0, "vr_bootstrap_spearman_multi_joined: null idx");
-  const int64_t total = n_sets + (full_first ? 1 : 0);
-  VR_REQUIRE(n_b <= 1 || ld_scores >= total, "vr_bootstrap_spearman_multi_joined: ld_scores %lld < %lld",
-             (long long)ld_scores, (long long)total);
-  for (int64_t j = 0; j < n_b; ++j)
-    VR_REQUIRE(planBs[j] != nullptr, "vr_bootstrap_spearman_multi_joined: planBs[%lld] is null", (long long)j);
-  VR_REQUIRE(n_b == 0 || posA != nullptr, "vr_bootstrap_spearman_multi_joined: null posA");
-  for (int64_t j = 0; j < n_b; ++j)
-    VR_REQUIRE(posA[j] != nullptr, "vr_bootstrap_spearman_multi_joined: posA[%lld] is null", (long long)j);
-  EngineCfg cfg = engine_cfg(n);
-  cfg.prejoined = true;
-  const size_t need = multi_layout(nullptr, n, n_b, cfg.nwaves, nullptr, nullptr, true);
-  if (ws_bytes < need || ws == nullptr) {
-    set_error("vr_bootstrap_spearman_multi_joined: workspace %zu < %zu", ws_bytes, need);
-    return VR_EWORKSPACE;
-  }
-  EngineWs E;
-  std::vector<uint32_t*> joins;
-  multi_layout(ws, n, n_b, cfg.nwaves, &E, &joins, true);
-  for (int64_t j = 0; j < n_b; ++j) joins[(size_t)(2 * j)] = posA[j];
-  const PlanView A = plan_layout(const_cast<void*>(planA), n);
-  std::vector<PlanView> Bs;
-  for (int64_t j = 0; j < n_b; ++j) Bs.push_back(plan_layout(const_cast<void*>(planBs[j]), n));
-  return run_engine_multi(A, Bs.data(), n_b, n, idx, k, n_sets, full_first, scores, ld_scores,
-                          joins.data(), E, LANES, cfg, as_stream(stream));
+  return multi_entry("vr_bootstrap_spearman_multi_joined", true, planA, planBs, n_b, n, idx, k, n_sets, full_first,
+                     scores, ld_scores, posA, ws, ws_bytes, stream);
 }
 
 // A grid call's workspace: region 0's full joined-multi layout, then one slim layout (u16 TB,
@@ -2556,26 +2579,14 @@ int vr_bootstrap_spearman_grid_joined(const void* const* planAs, int64_t n_a, co
                                       double* scores, int64_t ld_scores, uint32_t* const* posA, void* ws,
                                       size_t ws_bytes, void* stream) {
   const char* fn = "vr_bootstrap_spearman_grid_joined";
-  VR_REQUIRE(n >= 0 && n <= 65535, "%s: n=%lld out of range", fn, (long long)n);
-  VR_REQUIRE(n_a >= 1 && n_a <= 4, "%s: n_a=%lld not in [1, 4]", fn, (long long)n_a);
-  VR_REQUIRE(n_b >= 0, "%s: n_b=%lld", fn, (long long)n_b);
-  VR_REQUIRE(planAs && (n_b == 0 || (planBs && scores && posA)), "%s: null pointer", fn);
-  VR_REQUIRE(k >= 0 && k <= n && n_sets >= 0, "%s: bad k=%lld sets=%lld", fn, (long long)k, (long long)n_sets);
-  VR_REQUIRE(idx != nullptr || n_sets == 0 || k == 0, "%s: null idx", fn);
-  const int64_t total = n_sets + (full_first ? 1 : 0);
-  VR_REQUIRE(ld_scores >= total, "%s: ld_scores %lld < %lld", fn, (long long)ld_scores, (long long)total);
-  for (int64_t i = 0; i < n_a; ++i) VR_REQUIRE(planAs[i] != nullptr, "%s: planAs[%lld] is null", fn, (long long)i);
-  for (int64_t j = 0; j < n_b; ++j) VR_REQUIRE(planBs[j] != nullptr, "%s: planBs[%lld] is null", fn, (long long)j);
+  VR_TRY(check_args(fn, n, n_a, n_b, planAs && (n_b == 0 || (planBs && scores && posA)), idx, k, n_sets, full_first,
+                    true, ld_scores, planAs, planBs));
   for (int64_t u = 0; u < n_a * n_b; ++u) VR_REQUIRE(posA[u] != nullptr, "%s: posA[%lld] is null", fn, (long long)u);
   EngineCfg cfg = engine_cfg(n);
   cfg.prejoined = true;
   const size_t full = multi_layout(nullptr, n, n_b, cfg.nwaves, nullptr, nullptr, true);
   const size_t slim = grid_slim_bytes(n, n_b, cfg.nwaves);
-  const size_t need = full + (size_t)(n_a - 1) * slim;
-  if (ws == nullptr || ws_bytes < need) {
-    set_error("%s: workspace %zu < %zu", fn, ws_bytes, need);
-    return VR_EWORKSPACE;
-  }
+  VR_TRY(check_ws(fn, ws, ws_bytes, full + (size_t)(n_a - 1) * slim));
   std::vector<EngineWs> E((size_t)n_a);
   std::vector<uint32_t*> j0;
   multi_layout(ws, n, n_b, cfg.nwaves, &E[0], &j0, true);
@@ -2586,16 +2597,13 @@ int vr_bootstrap_spearman_grid_joined(const void* const* planAs, int64_t n_a, co
   // written when a region runs on its own)
   std::vector<std::vector<uint32_t*>> jv((size_t)n_a, j0);
   std::vector<uint32_t* const*> joins((size_t)n_a);
-  std::vector<PlanView> As;
   for (int64_t i = 0; i < n_a; ++i) {
     for (int64_t j = 0; j < n_b; ++j) jv[(size_t)i][(size_t)(2 * j)] = posA[i * n_b + j];
     joins[(size_t)i] = jv[(size_t)i].data();
-    As.push_back(plan_layout(const_cast<void*>(planAs[i]), n));
   }
-  std::vector<PlanView> Bs;
-  for (int64_t j = 0; j < n_b; ++j) Bs.push_back(plan_layout(const_cast<void*>(planBs[j]), n));
-  return run_engine_grid(As.data(), (int)n_a, Bs.data(), n_b, n, idx, k, n_sets, full_first, scores, ld_scores,
-                         joins.data(), E.data(), cfg, as_stream(stream));
+  const std::vector<PlanView> As = plan_views(planAs, n_a, n), Bs = plan_views(planBs, n_b, n);
+  return run_engine_grid(engine_call(n, idx, k, n_sets, full_first, LANES, cfg, stream), As.data(), (int)n_a,
+                         Bs.data(), n_b, scores, ld_scores, joins.data(), E.data());
 }
 
 size_t vr_engine_posmap4_bytes(int64_t n) { return (size_t)pairs_of(n) * sizeof(uint4); }
@@ -2636,6 +2644,21 @@ int vr_engine_join4(const void* posmap4, int64_t n_a, const void* planB, int64_t
   return VR_OK;
 }
 
+// One-shot calls: both plans built in the workspace, then one unit with lw subsets per pass
+static int oneshot(const char* fn, const float* A, const float* B, int64_t n, int64_t ld, const int32_t* idx, int64_t k,
+                   int64_t n_sets, int full_first, int lw, double* scores, void* ws, size_t ws_bytes, void* stream) {
+  const EngineCfg cfg = engine_cfg(n);
+  VR_TRY(check_ws(fn, ws, ws_bytes, oneshot_bytes(n, lw, cfg.nwaves, nullptr, nullptr, nullptr, nullptr, nullptr)));
+  PlanView PA, PB;
+  PlanBuildWs W;
+  EngineWs E;
+  oneshot_bytes(n, lw, cfg.nwaves, ws, &PA, &PB, &W, &E);
+  const EngineCall c = engine_call(n, idx, k, n_sets, full_first, lw, cfg, stream);
+  VR_TRY(build_plan(A, n, ld, PA, W, c.st));
+  VR_TRY(build_plan(B, n, ld, PB, W, c.st));
+  return run_engine(c, PA, PB, scores, E);
+}
+
 size_t vr_bootstrap_spearman_workspace(int64_t n) {
   n = n < 0 ? 0 : n;
   return oneshot_bytes(n, LANES, engine_cfg(n).nwaves, nullptr, nullptr, nullptr, nullptr, nullptr);
@@ -2647,20 +2670,8 @@ int vr_bootstrap_spearman_f32(const float* A, const float* B, int64_t n, int64_t
   VR_REQUIRE(n >= 0 && n <= 65535 && ld >= n, "vr_bootstrap_spearman_f32: bad shape");
   VR_REQUIRE(k >= 0 && k <= n && n_sets >= 0, "vr_bootstrap_spearman_f32: bad k");
   VR_REQUIRE(scores != nullptr, "vr_bootstrap_spearman_f32: null scores");
-  const EngineCfg cfg = engine_cfg(n);
-  const size_t need = oneshot_bytes(n, LANES, cfg.nwaves, nullptr, nullptr, nullptr, nullptr, nullptr);
-  if (ws_bytes < need || ws == nullptr) {
-    set_error("vr_bootstrap_spearman_f32: workspace %zu < %zu", ws_bytes, need);
-    return VR_EWORKSPACE;
-  }
-  PlanView PA, PB;
-  PlanBuildWs W;
-  EngineWs E;
-  oneshot_bytes(n, LANES, cfg.nwaves, ws, &PA, &PB, &W, &E);
-  hipStream_t st = as_stream(stream);
-  VR_TRY(build_plan(A, n, ld, PA, W, st));
-  VR_TRY(build_plan(B, n, ld, PB, W, st));
-  return run_engine(PA, PB, n, idx, k, n_sets, full_first, scores, E, LANES, cfg, st);
+  return oneshot("vr_bootstrap_spearman_f32", A, B, n, ld, idx, k, n_sets, full_first, LANES, scores, ws, ws_bytes,
+                 stream);
 }
 
 size_t vr_spearman_triu_workspace(int64_t n) {
@@ -2673,20 +2684,7 @@ int vr_spearman_triu_f32(const float* A, const float* B, int64_t n, int64_t ld, 
   VR_REQUIRE(n >= 0 && n <= 65535 && ld >= n, "vr_spearman_triu_f32: bad shape n=%lld ld=%lld",
              (long long)n, (long long)ld);
   VR_REQUIRE(out != nullptr, "vr_spearman_triu_f32: null out");
-  const EngineCfg cfg = engine_cfg(n);
-  const size_t need = oneshot_bytes(n, 1, cfg.nwaves, nullptr, nullptr, nullptr, nullptr, nullptr);
-  if (ws_bytes < need || ws == nullptr) {
-    set_error("vr_spearman_triu_f32: workspace %zu < %zu", ws_bytes, need);
-    return VR_EWORKSPACE;
-  }
-  PlanView PA, PB;
-  PlanBuildWs W;
-  EngineWs E;
-  oneshot_bytes(n, 1, cfg.nwaves, ws, &PA, &PB, &W, &E);
-  hipStream_t st = as_stream(stream);
-  VR_TRY(build_plan(A, n, ld, PA, W, st));
-  VR_TRY(build_plan(B, n, ld, PB, W, st));
-  return run_engine(PA, PB, n, nullptr, 0, 0, 1, out, E, 1, cfg, st);
+  return oneshot("vr_spearman_triu_f32", A, B, n, ld, nullptr, 0, 0, 1, 1, out, ws, ws_bytes, stream);
 }
 
 }  // extern "C"
