@@ -75,7 +75,9 @@ class DeviceTransform:
         H, W, _ = arrs[0].shape
         src = torch.from_numpy(np.stack(arrs)).to(dev, non_blocking=True)
         if not self.preprocess:  # transforms.ToTensor() only: one fp32 division per value
-            return src.permute(0, 3, 1, 2).float().div(255)
+            # The divisor is a device tensor: torch divides by a Python scalar as a multiplication
+            # by its reciprocal, which is off by one ulp from v / 255 for 126 of the 256 values.
+            return src.permute(0, 3, 1, 2).float().div(torch.tensor(255.0, device=dev))
         out = torch.empty((B, 3, self.crop, self.crop), dtype=torch.float32, device=dev)
         L = lib()
         f = self.FILTERS[self.interpolation]
