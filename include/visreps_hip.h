@@ -857,6 +857,44 @@ int vr_plssvd_folds_svd_f64(const float* X, int64_t ldx, const float* Y, int64_t
                             void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------
+ * Label-conditioned statistics (csrc/class_stats.hip): the per-class, per-feature sums behind the
+ * Fisher ratio, class selectivity and centroid analyses, and two per-row reductions.
+ * Replaces the per-batch host copy + np.add.at of class_selectivity_index.py:130-173 and the
+ * boolean-mask loops of task_brain_alignment.py:126-195 and variance_ratio.py:31-42.
+ * -------------------------------------------------------------------------- */
+/* Per-class moments of X [dev] (n, d) fp32 row-major, ldx >= d, under labels [dev] int32 (n):
+ * sum[c][j] = sum over the rows i of class c of (x_ij - centre[c][j]), sumsq[c][j] the same of
+ * the squares; the subtraction and the product in fp64 (the square enters by one fused
+ * multiply-add). centre [dev] (C, d) doubles, null = 0;
+ * counts [dev] int64 (C); sum [dev] (C, d) doubles; sumsq the same, nullable; skipped [dev] one
+ * int64: rows whose label is outside [0, C), which are counted there and never read.
+ * Summation order (the contract): a class's rows in ascending row index, cut into chunks of
+ * R = vr_class_moments_chunk_rows() rows, added one after the other inside a chunk, chunk
+ * partials added in ascending order. The result is a function of X and of each class's own row
+ * order alone: bit-identical run to run, no floating-point atomics. accumulate = 0 overwrites
+ * every output (an empty class gets 0); accumulate = 1 adds this call's totals onto counts, sum,
+ * sumsq and skipped, one fp64 add per entry of a class that has rows. n = 0 writes zeros (nothing
+ * when accumulating). A NaN or inf entry reaches its own (class, column) entries only.
+ * VR_EINVAL for n < 0, n > 2^31 - 1, d < 1, d > 2^21, C < 1, ldx < d or a null pointer;
+ * VR_EWORKSPACE for ws_bytes below vr_class_moments_workspace(n, d, C): the pairs sort plus
+ * (n / R + min(C, n)) d chunk partials of 16 bytes, non-decreasing in n, d and C (0 for a bad
+ * shape). No host synchronisation. */
+int64_t vr_class_moments_chunk_rows(void);
+size_t vr_class_moments_workspace(int64_t n, int64_t d, int64_t C);
+int vr_class_moments_f32(const float* X, int64_t n, int64_t d, int64_t ldx, const int32_t* labels,
+                         int64_t C, const double* centre, int64_t* counts, double* sum, double* sumsq,
+                         int64_t* skipped, int accumulate, void* ws, size_t ws_bytes, void* stream);
+/* dist [dev] n doubles: dist[i] = || x_i - centre[labels[i]] ||_2 in fp64, NaN for a label outside
+ * [0, C). One wave per row: lane l adds the 4-column groups l, l + 64, ... in ascending order, the
+ * 64 partials meet in a fixed tree; the bits do not depend on ldx or alignment. centre non-null. */
+int vr_class_dist_f32(const float* X, int64_t n, int64_t d, int64_t ldx, const int32_t* labels,
+                      int64_t C, const double* centre, double* dist, void* stream);
+/* Per row of X: l1 [dev] n doubles = sum |x|, l2 = sqrt(sum x^2), both in fp64 in the order of
+ * vr_class_dist_f32; active [dev] n int64 = #{j: |x_ij| > threshold} (a NaN entry is not counted). */
+int vr_row_sparsity_f32(const float* X, int64_t n, int64_t d, int64_t ldx, float threshold, double* l1,
+                        double* l2, int64_t* active, void* stream);
+
+/* ------------------------------------------------------------------------------
  * Host: legacy numpy RandomState (MT19937) index streams, bit-exact.
  * Replaces np.random.RandomState(seed) + .choice(n, k, replace=False) / .permutation(n)
  * (evals.py:260-261,356,362-364; rsa.py:169,176,248-250; evals.py:111-113).

@@ -307,6 +307,14 @@ _PROTOTYPES = {
         [_vp, _c_i64, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _c_i64,
          _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _c_sz, _vp],
     ),
+    "vr_class_moments_chunk_rows": (_c_i64, []),
+    "vr_class_moments_workspace": (_c_sz, [_c_i64, _c_i64, _c_i64]),
+    "vr_class_moments_f32": (
+        ctypes.c_int,
+        [_vp, _c_i64, _c_i64, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, _vp, _c_sz, _vp],
+    ),
+    "vr_class_dist_f32": (ctypes.c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _c_i64, _vp, _vp, _vp]),
+    "vr_row_sparsity_f32": (ctypes.c_int, [_vp, _c_i64, _c_i64, _c_i64, ctypes.c_float, _vp, _vp, _vp, _vp]),
     "vr_legacy_choice": (ctypes.c_int, [ctypes.c_uint32, _c_i64, _c_i64, _c_i64, _vp]),
     "vr_percentile_linear": (ctypes.c_double, [_vp, _c_i64, ctypes.c_double]),
 }

@@ -226,6 +226,14 @@ size_t radix_ws_elems(int64_t n) {
   return (size_t)(256 * nb + 64) + (size_t)256 * rs_chunks(nb).c + 256;
 }
 
+// rs_chunks(nb).c is at most min(nb / 16 + 1, 1024) and that cap never shrinks as nb grows, which
+// the chunk count itself does where the chunk length steps up.
+size_t radix_ws_elems_bound(int64_t n) {
+  const int64_t nb = (n + RS_TILE - 1) / RS_TILE;
+  const int64_t c = nb / 16 + 1 < 1024 ? nb / 16 + 1 : 1024;
+  return (size_t)(256 * nb + 64) + (size_t)256 * c + 256;
+}
+
 int radix_offsets(const uint32_t* ki, int64_t n, int shift, uint32_t* ws, hipStream_t st) {
   if (n <= 0) return VR_OK;
   const int64_t nb = (n + RS_TILE - 1) / RS_TILE;
